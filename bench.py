@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — batched 1-D rfft throughput on MI355X (BASELINE.json's metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path over one batch already resident in HBM:
 dsc_rfft of a [8192, 65536] f32 tensor into a [8192, 32769] c32 tensor through the C ABI
@@ -22,6 +22,7 @@ Prints ONE JSON line on rank 0.  Extra keys beyond the driver's contract:
   parity        SURVEY 8d's on-device check (untimed): first / last 4 rows + 64 seeded random rows against the CPU oracle, and
                 Parseval's identity on ALL rows, evaluated on the device with the product's own dsc_mul / dsc_conj / dsc_sum
   min_ms, median_ms   per-step HIP-event times of the K timed steps (the reference reports the minimum, utils.py:11-12)
+  dump_outputs  with --dump-outputs DIR only: the files written there (the spectrum of the last timed step, a fixed row sample)
   config4_on_one_gpu  N == 1 only: the 65536 rows of BASELINE configs[3] as 8 sequential 8192-row launches on this GPU — the
                 like-for-like denominator of the 8-GPU line
 """
@@ -41,6 +42,8 @@ N_FFT = 65536
 BATCH = 8192
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
 BYTES_PER_ROW = N_FFT * 4 + (N_FFT // 2 + 1) * 8      # 524,296 B: 4 B/sample in + 8 B/bin out
+DUMP_BYTES = 64 * 10 ** 6        # --dump-outputs: all files together, all ranks
+DUMP_SEED = 2718                 # --dump-outputs: the row sample
 
 
 @contextlib.contextmanager
@@ -100,6 +103,38 @@ def cpu_baseline(rows=1024, reps=5, warm=2):
     }
 
 
+def spectrum_rows(dsc, B, ctx, out, pick):
+    """Rows `pick` of the [rows, N/2 + 1] c32 spectrum on the device, copied to the host one row view at a time."""
+    import ctypes
+    import numpy as np
+    bins = N_FFT // 2 + 1
+    o_ptr = out._c_ptr.contents.data
+    got = np.empty((len(pick), bins), np.complex64)
+    shp1 = (ctypes.c_int * 2)(1, bins)
+    for i, r in enumerate(pick):
+        v = B.dsc_tensor_from_device_ptr(ctx, o_ptr + r * bins * 8, bins * 8, 2, shp1, int(dsc.Dtype.C32))
+        B.dsc_copy_to_host(ctx, v, got[i].ctypes.data, bins * 8)
+        B.dsc_tensor_free(ctx, v)
+    return got
+
+
+def dump_outputs(dsc, B, ctx, out, rows, rank, world, directory):
+    """--dump-outputs: what the timed rfft wrote in its last step, as float32 [k, N/2 + 1, 2] (re, im) in
+    DIR/rfft.npy (DIR/rfft_rank<r>.npy for N > 1).  The whole spectrum is 2 GiB, so k rows: every row while the files
+    stay within DUMP_BYTES in all, else the same seeded sample of rows on every run."""
+    import numpy as np
+    row_bytes = (N_FFT // 2 + 1) * 8
+    k = min(rows, DUMP_BYTES // world // row_bytes)
+    pick = list(range(rows)) if k == rows else sorted(int(r) for r in np.random.default_rng(DUMP_SEED).choice(rows, k, replace=False))
+    spec = spectrum_rows(dsc, B, ctx, out, pick)
+    name = 'rfft.npy' if world == 1 else f'rfft_rank{rank}.npy'
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name), spec.view(np.float32).reshape(k, N_FFT // 2 + 1, 2))
+    return {'dir': directory, 'files': ['rfft.npy'] if world == 1 else [f'rfft_rank{r}.npy' for r in range(world)],
+            'layout': f'float32 [{k}, {N_FFT // 2 + 1}, 2] per rank: (re, im) of the last timed step\'s spectrum',
+            'rows': 'all' if k == rows else f'{k} of {rows} per rank, numpy default_rng({DUMP_SEED}).choice without replacement, sorted'}
+
+
 def device_parity(dsc, B, ctx, x, out, x_host, rows, rank):
     """SURVEY 8d, untimed.  (1) first / last 4 rows + 64 seeded random rows of the spectrum on the device against the CPU oracle
     (rel-L2 per row, tolerance 1e-5).  (2) Parseval on EVERY row with the product's own operators:
@@ -112,12 +147,7 @@ def device_parity(dsc, B, ctx, x, out, x_host, rows, rank):
     rng = np.random.default_rng(4321 + rank)
     pick = sorted(set(list(range(min(4, rows))) + list(range(max(0, rows - 4), rows)) + [int(r) for r in rng.integers(0, rows, size=min(64, rows))]))
     x_ptr, o_ptr = x._c_ptr.contents.data, out._c_ptr.contents.data
-    got = np.empty((len(pick), bins), np.complex64)
-    shp1 = (ctypes.c_int * 2)(1, bins)
-    for i, r in enumerate(pick):
-        v = B.dsc_tensor_from_device_ptr(ctx, o_ptr + r * bins * 8, bins * 8, 2, shp1, int(dsc.Dtype.C32))
-        B.dsc_copy_to_host(ctx, v, got[i].ctypes.data, bins * 8)
-        B.dsc_tensor_free(ctx, v)
+    got = spectrum_rows(dsc, B, ctx, out, pick)
     want = port.rfft(x_host[pick])
     per_row = np.linalg.norm(got - want, axis=1) / np.linalg.norm(want, axis=1)
     # Parseval, all rows, on the device
@@ -317,7 +347,13 @@ def main():
     ap.add_argument('--backend', default='nccl', help='torch.distributed backend (gloo for the CPU dry run)')
     ap.add_argument('--dry-run', action='store_true', help='exercise the multi-process plumbing without a GPU (tests)')
     ap.add_argument('--share-device', action='store_true', help='testing aid: every rank uses device 0 (rehearse N > 1 on a one-GPU box; use with --backend gloo)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write the spectrum the last one computed to DIR/rfft.npy '
+                                                         '(float32 (re, im); a fixed, seeded sample of rows, at most 64 MB in all)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_outputs and args.dry_run:
+        ap.error('--dump-outputs needs the device: a dry run computes nothing')
 
     rank = int(os.environ.get('RANK', '0'))
     local_rank = int(os.environ.get('LOCAL_RANK', '0'))
@@ -411,6 +447,11 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device='cpu' if args.dry_run or args.backend == 'gloo' else 'cuda')
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # ---- --dump-outputs: the spectrum of the last timed step, before anything else runs on these buffers (untimed)
+    if args.dump_outputs:
+        with c_stdout_to_stderr():
+            extra['dump_outputs'] = dump_outputs(dsc, B, ctx, out, rows, rank, world, args.dump_outputs)
 
     # ---- the other kernels of the hot path (configs[1] irfft on the same buffers, configs[2] fused filter on half the batch,
     # configs[4] rfft f64 N=262144): each a full roofline object, reported next to the metric, never part of `value`

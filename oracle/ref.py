@@ -2,7 +2,7 @@
 oracle/Makefile (`make ref`) from the sources where they lie under /root/reference.
 
 TEST INFRASTRUCTURE ONLY.  Used to pin the C restatement (tests/test_oracle_vs_ref.py),
-to generate tests/golden/ (tests/golden/make_golden.py) and, on the GPU box, as the
+to generate tests/golden/ (tests/golden/make_golden.py, make_ref_calls.py) and, on the GPU box, as the
 "reference" CPU baseline in bench.py.  The .so is git-ignored but travels with gpurun;
 the reference's sources never leave /root/reference.
 

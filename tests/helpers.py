@@ -1,10 +1,14 @@
 """Shared test helpers: deterministic signals, golden-fixture access, error metrics."""
+import hashlib
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, 'golden')
 NP = {'f32': np.float32, 'f64': np.float64, 'c32': np.complex64, 'c64': np.complex128}
 
@@ -97,3 +101,125 @@ class Golden:
 def decode_sel(sel):
     """`sel` of a 'slice' golden record -> tuple of ints / slices (tests/golden/make_golden.py)."""
     return tuple(slice(*k) if isinstance(k, list) else int(k) for k in sel)
+
+
+def digest(a):
+    """SHA-256 of an array's dtype, shape and bytes."""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256(f'{a.dtype.str} {a.shape} '.encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _args_digest(op, args):
+    h = hashlib.sha256(op.encode())
+    for a in args:
+        h.update((digest(a) if isinstance(a, np.ndarray) else repr(a)).encode())
+    return h.hexdigest()[:16]
+
+
+class Pinned:
+    """A large reference output kept as its digest only: the only comparison it allows is bit for bit."""
+
+    def __init__(self, shape, dtype, sha):
+        self.shape, self.dtype, self.sha = tuple(shape), np.dtype(dtype), sha
+
+    def matches(self, a):
+        return a.shape == self.shape and a.dtype == self.dtype and digest(a) == self.sha
+
+
+class RefRecording:
+    """tests/golden/ref_calls.{json,npz}: per test, every call it made on the reference build (oracle/_ref) with a digest
+    of the call's inputs and the reference's output — whole up to FULL_BYTES, as a digest (Pinned) above that.
+    Written by tests/golden/make_ref_calls.py."""
+
+    PATH = os.path.join(GOLDEN, 'ref_calls')
+    FULL_BYTES = 32 << 10
+
+    def __init__(self, empty=False):
+        self.calls, self.arrays = {}, {}
+        if not empty:
+            with open(self.PATH + '.json') as f:
+                self.calls = json.load(f)
+            with np.load(self.PATH + '.npz') as z:
+                self.arrays = {k: z[k] for k in z.files}
+
+    def save(self):
+        with open(self.PATH + '.json', 'w') as f:
+            json.dump(self.calls, f, indent=0, sort_keys=True)
+            f.write('\n')
+        np.savez_compressed(self.PATH + '.npz', **self.arrays)
+
+
+class RecordedRef:
+    """Stands in for oracle.ref.Ref (same methods) in tests/test_oracle_vs_ref.py: call i of a test returns what the
+    reference returned for call i of the same test when it was recorded.  The tests' inputs are seeded; their digest is
+    checked call by call, so a changed test cannot be compared against a stale recording.
+
+    Where the reference build exists (oracle/_ref), every call is also made on it and must reproduce the recording bit
+    for bit.  With `recording` given, the reference's outputs are written into it instead (make_ref_calls.py)."""
+
+    OPS = ('fft', 'ifft', 'rfft', 'irfft', 'mul', 'binary', 'unary', 'reduce', 'cast', 'get_slice', 'set_slice')
+    _shared = None
+
+    def __init__(self, test, recording=None):
+        from oracle import ref
+        self.test, self.i = test, 0
+        self.live = ref.Ref.get() if ref.available() else None
+        self.record = recording is not None
+        if self.record:
+            if self.live is None:
+                raise RuntimeError(f'{ref.LIB_PATH} missing: recording needs the reference build')
+            self.rec = recording
+            self.rec.calls[test] = []
+        else:
+            if RecordedRef._shared is None:
+                RecordedRef._shared = RefRecording()
+            self.rec = RecordedRef._shared
+        self.calls = self.rec.calls.get(test)
+        assert self.calls is not None, f'{test}: not in {RefRecording.PATH}.json (run tests/golden/make_ref_calls.py)'
+
+    def _next(self, op, args):
+        key = _args_digest(op, args)
+        if self.record:
+            self.calls.append({'op': op, 'args': key})
+        assert self.i < len(self.calls), f'{self.test}: more calls than recorded (run tests/golden/make_ref_calls.py)'
+        c = self.calls[self.i]
+        assert (c['op'], c['args']) == (op, key), \
+            f'{self.test}: call {self.i} ({op}) has other inputs than the recording (run tests/golden/make_ref_calls.py)'
+        self.i += 1
+        return c
+
+    def __getattr__(self, op):
+        if op not in self.OPS:
+            raise AttributeError(op)
+
+        def call(*args):
+            i = self.i
+            c = self._next(op, args)
+            if self.live is not None:
+                y = getattr(self.live, op)(*args)
+                if self.record:
+                    c['sha'] = digest(y)
+                    if y.nbytes <= RefRecording.FULL_BYTES:
+                        self.rec.arrays[f'{self.test}.{i}'] = y
+                    else:
+                        c.update(shape=list(y.shape), dtype=y.dtype.str)
+                assert digest(y) == c['sha'], f'{self.test}: call {i} ({op}): the reference build no longer gives the recorded output'
+            key = f'{self.test}.{i}'
+            if key in self.rec.arrays:
+                return self.rec.arrays[key].copy()
+            return Pinned(c['shape'], c['dtype'], c['sha'])
+        return call
+
+    def ends_process(self, call):
+        """Does `r.<call>` on the reference end a fresh process (the reference's DSC_ASSERT prints and exits)?"""
+        c = self._next('ends_process', (call,))
+        if self.live is not None:
+            code = f'import numpy as np\nfrom oracle import ref\nr = ref.Ref.get(1 << 26, 1 << 24)\nr.{call}\nprint("SURVIVED")'
+            p = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, cwd=ROOT)
+            ended = p.returncode != 0 and 'SURVIVED' not in p.stdout
+            if self.record:
+                c['ended'] = ended
+            assert ended == c['ended'], (call, p.stdout, p.stderr[-300:])
+        return c['ended']

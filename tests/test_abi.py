@@ -57,9 +57,11 @@ def test_header_is_plain_c():
 
 def test_no_gpu_is_a_loud_error_not_a_fallback():
     """Without a device, dsc_ctx_init must die (reference error convention: stderr + exit),
-    never compute on the CPU."""
-    import torch
-    if torch.cuda.is_available():
+    never compute on the CPU.  The GPU probe runs in its own process: torch imported here, after this module loaded the
+    library, would bring its own copy of the HIP runtime into the test process and break the GPU tests that follow."""
+    probe = subprocess.run([sys.executable, '-c', 'import torch; print(torch.cuda.is_available())'], capture_output=True, text=True)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1] == 'True':
         pytest.skip('GPU present')
     code = ('import ctypes; L = ctypes.CDLL(%r); L.dsc_ctx_init.restype = ctypes.c_void_p; '
             'L.dsc_ctx_init.argtypes = [ctypes.c_size_t] * 2; L.dsc_ctx_init(1 << 20, 1 << 20); print("ALIVE")' % LIB)

@@ -44,3 +44,12 @@ def test_single_process_requires_launcher():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dry-run'],
                        capture_output=True, text=True, timeout=120, cwd=ROOT)
     assert r.returncode != 0 and 'torch.distributed.run' in r.stderr
+
+
+def test_arguments_are_checked():
+    """--steps sets the number of timed steps, so it must be at least one; --dump-outputs needs device work to dump."""
+    for extra in (['--steps', '0'], ['--warmup', '-1'], ['--dump-outputs', 'unused']):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--dry-run'] + extra,
+                           capture_output=True, text=True, timeout=120, cwd=ROOT)
+        assert r.returncode == 2 and 'error' in r.stderr, (extra, r.stderr)
+    assert not os.path.exists(os.path.join(ROOT, 'unused'))

@@ -192,6 +192,38 @@ def test_bench_two_ranks_on_one_gpu():
     assert g['variants']['ipc']['memory'] == 'device' and g['verified'] is True
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs DIR: the spectrum of the last timed step as float32 (re, im) of a seeded row sample, at most
+    64 MB; the sampled rows agree with the CPU oracle, and two runs with the same arguments write the same bytes."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from oracle import port
+    import bench
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f'run{run}'
+        cmd = [sys.executable, os.path.join(root, 'bench.py'), '--steps', '3', '--warmup', '1', '--batch', '1024', '--ramp-ms', '0',
+               '--no-other-kernels', '--no-cpu-baseline', '--chunks', '0', '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
+        assert len(lines) == 1, r.stdout
+        j = json.loads(lines[0])
+        assert j['steps'] == 3 and j['dump_outputs']['files'] == ['rfft.npy'] and os.listdir(d) == ['rfft.npy']
+        assert os.path.getsize(d / 'rfft.npy') <= 64 * 10 ** 6
+        dumps.append(np.load(d / 'rfft.npy'))
+    got = dumps[0]
+    k = bench.DUMP_BYTES // ((bench.N_FFT // 2 + 1) * 8)
+    assert got.dtype == np.float32 and got.shape == (k, bench.N_FFT // 2 + 1, 2)
+    assert np.array_equal(dumps[0], dumps[1])
+    pick = sorted(np.random.default_rng(bench.DUMP_SEED).choice(1024, k, replace=False))
+    want = port.rfft(bench.synthetic_rows(1024, 0)[pick])
+    assert_close(got.view(np.complex64)[..., 0], want, what='dumped spectrum rows')
+
+
 def test_f64_262144_register_path(dsc):
     """BASELINE config 5 (f64 N=262144) on the team kernel of fft_xcd_fused.hip (one cooperative launch: 512-point row tasks, 256-point
     column tasks with the packed-real pass fused, the four-step intermediate in the XCD-local L2).  Parity 1e-12 vs the oracle, round
