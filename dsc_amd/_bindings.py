@@ -78,6 +78,19 @@ dsc_mul = _sig('dsc_mul', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _Ds
 dsc_add = _sig('dsc_add', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _DscTensor_p)
 dsc_sub = _sig('dsc_sub', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _DscTensor_p)
 dsc_div = _sig('dsc_div', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _DscTensor_p)
+dsc_pow = _sig('dsc_pow', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _DscTensor_p)
+dsc_cos = _sig('dsc_cos', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_sin = _sig('dsc_sin', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_sinc = _sig('dsc_sinc', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_logn = _sig('dsc_logn', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_log2 = _sig('dsc_log2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_log10 = _sig('dsc_log10', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_exp = _sig('dsc_exp', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_sqrt = _sig('dsc_sqrt', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
+dsc_i0 = _sig('dsc_i0', _DscTensor_p, _DscCtx, _DscTensor_p)
+dsc_clip = _sig('dsc_clip', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_double, c_double)
+dsc_arange = _sig('dsc_arange', _DscTensor_p, _DscCtx, c_int, c_uint8)
+dsc_randn = _sig('dsc_randn', _DscTensor_p, _DscCtx, c_int, POINTER(c_int), c_uint8)
 dsc_abs = _sig('dsc_abs', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p)
 dsc_angle = _sig('dsc_angle', _DscTensor_p, _DscCtx, _DscTensor_p)
 dsc_conj = _sig('dsc_conj', _DscTensor_p, _DscCtx, _DscTensor_p)
@@ -127,6 +140,18 @@ _dsc_transpose = _sig('dsc_transpose', _DscTensor_p, _DscCtx, _DscTensor_p, c_in
 
 def dsc_transpose(ctx, x, *axes):
     return _dsc_transpose(ctx, x, len(axes), *[c_int(a) for a in axes])
+
+
+_dsc_reshape = _sig('dsc_reshape', _DscTensor_p, _DscCtx, _DscTensor_p, c_int)
+_dsc_concat = _sig('dsc_concat', _DscTensor_p, _DscCtx, c_int, c_int)
+
+
+def dsc_reshape(ctx, x, *dims):
+    return _dsc_reshape(ctx, x, len(dims), *[c_int(d) for d in dims])
+
+
+def dsc_concat(ctx, axis, *tensors):
+    return _dsc_concat(ctx, axis, len(tensors), *tensors)
 
 
 dsc_fftfreq = _sig('dsc_fftfreq', _DscTensor_p, _DscCtx, c_int, c_double, c_uint8)

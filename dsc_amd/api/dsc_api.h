@@ -1,8 +1,8 @@
 // dsc_api.h — header-only C++ wrapper over the C ABI in include/dsc_mi355x.h.
 //
-// Mirror of the reference's dsc/api/dsc_api.h for the hot-path subset: `dsc::init`, RAII
-// `dsc::tensor<T>`, `operator*`, `dsc::sum`, `dsc::fft / ifft / rfft / irfft` (reference
-// lines 15-21, 24-34, 36-143, 148-186, 285-302, 321-343) plus `dsc::filter_fft`.  The one semantic
+// Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
+// `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -187,6 +187,45 @@ template<typename T>
 static inline tensor<T> rfft(const tensor<T> &x, int n = -1, int axis = -1) noexcept { return dsc_rfft(ctx, x.x_, nullptr, n, axis); }
 template<typename T>
 static inline tensor<T> irfft(const tensor<T> &x, int n = -1, int axis = -1) noexcept { return dsc_irfft(ctx, x.x_, nullptr, n, axis); }
+
+// dsc_api.h:187-189: x.pow(e) is a free function here, pow(x, e) / pow(x, y)
+template<typename T>
+static inline tensor<T> pow(const tensor<T> &x, const tensor<T> &e) noexcept { return dsc_pow(ctx, x.x_, e.x_, nullptr); }
+template<typename T>
+static inline tensor<T> pow(const tensor<T> &x, const T e) noexcept { return dsc_pow(ctx, x.x_, tensor<T>({e}).x_, nullptr); }
+
+// dsc_api.h:260-283: element-wise functions, i0, clip, arange
+template<typename T> static inline tensor<T> cos(const tensor<T> &x) noexcept { return dsc_cos(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> sin(const tensor<T> &x) noexcept { return dsc_sin(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> sinc(const tensor<T> &x) noexcept { return dsc_sinc(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> logn(const tensor<T> &x) noexcept { return dsc_logn(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> log2(const tensor<T> &x) noexcept { return dsc_log2(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> log10(const tensor<T> &x) noexcept { return dsc_log10(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> exp(const tensor<T> &x) noexcept { return dsc_exp(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> sqrt(const tensor<T> &x) noexcept { return dsc_sqrt(ctx, x.x_, nullptr); }
+template<typename T> static inline tensor<T> i0(const tensor<T> &x) noexcept { return dsc_i0(ctx, x.x_); }
+template<typename T>
+static inline tensor<T> clip(const tensor<T> &x, double x_min = -__builtin_inf(), double x_max = __builtin_inf()) noexcept {
+    return dsc_clip(ctx, x.x_, nullptr, x_min, x_max);
+}
+template<typename T>
+static inline tensor<T> arange(int n) noexcept { return dsc_arange(ctx, n, dtype_of<T>::value); }
+template<typename T>
+static inline tensor<T> randn(std::initializer_list<int> shape) noexcept {
+    const std::vector<int> s(shape);
+    return dsc_randn(ctx, (int) s.size(), s.data(), dtype_of<T>::value);
+}
+
+// dsc_api.h:304-319: reshape(x, 4, -1) shares x's buffer; concat(axis, a, b, ...) copies (axis = DSC_VALUE_NONE flattens)
+template<typename T, typename... Args>
+static inline tensor<T> reshape(const tensor<T> &x, Args... dimensions) noexcept {
+    static_assert((std::is_same_v<Args, int> && ...), "dimensions are ints");
+    return dsc_reshape(ctx, x.x_, (int) sizeof...(Args), dimensions...);
+}
+template<typename T, typename... Args>
+static inline tensor<T> concat(int axis, const tensor<T> &first, const Args &...rest) noexcept {
+    return dsc_concat(ctx, axis, 1 + (int) sizeof...(Args), first.x_, rest.x_...);
+}
 
 // README.md:141-163 (C++ filterFFT) as one call: y = irfft(rfft(s, n) * H)
 template<typename T>

@@ -1,13 +1,17 @@
-// dsc_capi.cpp — context, HBM arenas, tensors, copies, cast / mul / reductions of the C ABI
-// declared in include/dsc_mi355x.h.  FFT entry points live in fft_driver.cpp.
+// dsc_capi.cpp — context, HBM arenas, tensors, copies, creation (arange / randn), reshape / concat, cast, binary and
+// unary operators, reductions of the C ABI declared in include/dsc_mi355x.h.  FFT entry points live in fft_driver.cpp.
 //
 // Host-side mirror of dsc/src/dsc.cpp:136-470 (context + tensor creation), :44-115
-// (parameter validation), :1273-1284 (dsc_mul) and :1793-1953 (reductions); arithmetic is in
+// (parameter validation), :481-534 (arange / randn), :600-720 (reshape / concat), :1273-1297 (binary operators),
+// :1299-1440 and :1640-1770 (unary operators, i0, clip) and :1793-1953 (reductions); arithmetic is in
 // the .hip files.  Error behaviour is the reference's: print and exit (dsc.h:14-28).
 #include "dsc_internal.h"
 #include "kernels.h"
 
+#include <cstdarg>
 #include <cstring>
+#include <random>
+#include <vector>
 
 static int g_device = 0;
 
@@ -312,7 +316,7 @@ static const dsc_dtype k_promote[4][4] = {      // dsc_dtype.h:73-78
 static dsc_tensor *binary_entry(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out, int op) {
     DSC_ASSERT(xa != nullptr);
     DSC_ASSERT(xb != nullptr);
-    static const char *names[] = {"dsc_add", "dsc_sub", "dsc_mul", "dsc_div"};
+    static const char *names[] = {"dsc_add", "dsc_sub", "dsc_mul", "dsc_div", "dsc_pow"};
     dsc_trace_scope trace__(ctx, names[op], "op;binary", xa, xb);
     int shape[DSC_MAX_DIMS];
     for (int i = 0; i < DSC_MAX_DIMS; ++i) {       // can_broadcast, dsc.cpp:1174-1184
@@ -393,13 +397,17 @@ extern "C" dsc_tensor *dsc_mul(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc
 extern "C" dsc_tensor *dsc_add(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out) { return binary_entry(ctx, xa, xb, out, 0); }
 extern "C" dsc_tensor *dsc_sub(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out) { return binary_entry(ctx, xa, xb, out, 1); }
 extern "C" dsc_tensor *dsc_div(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out) { return binary_entry(ctx, xa, xb, out, 3); }
+// dsc.cpp:1299-1310 with pow_op (dsc_ops.h:305-316): every route of the other four, same result shape and dtype
+extern "C" dsc_tensor *dsc_pow(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out) { return binary_entry(ctx, xa, xb, out, 4); }
 
 // ------------------------------------------------------------------------------ unary (spectrum consumers)
 
 static dsc_dtype as_real(dsc_dtype t) { return dsc_is_single(t) ? DSC_F32 : DSC_F64; }
 
-static dsc_tensor *unary_entry(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int op, dsc_dtype out_dtype) {
-    static const char *names[] = {"dsc_abs", "dsc_angle", "dsc_conj", "dsc_real", "dsc_imag"};
+// op codes of dsc_launch_unary (kernels.h)
+static dsc_tensor *unary_entry(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int op, dsc_dtype out_dtype, double lo = 0, double hi = 0) {
+    static const char *names[] = {"dsc_abs", "dsc_angle", "dsc_conj", "dsc_real", "dsc_imag", "dsc_cos", "dsc_sin", "dsc_sinc",
+                                  "dsc_logn", "dsc_log2", "dsc_log10", "dsc_exp", "dsc_sqrt", "dsc_i0", "dsc_clip"};
     dsc_trace_scope trace__(ctx, names[op], "op;unary", x);
     if (out == nullptr) {
         out = dsc_new_tensor(ctx, x->n_dim, &x->shape[DSC_MAX_DIMS - x->n_dim], out_dtype, nullptr);
@@ -408,7 +416,7 @@ static dsc_tensor *unary_entry(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *ou
         DSC_ASSERT(out->n_dim == x->n_dim);
         DSC_ASSERT(memcmp(out->shape, x->shape, sizeof(x->shape)) == 0);
     }
-    dsc_launch_unary(x->data, x->dtype, out->data, op, x->ne, ctx->stream);
+    dsc_launch_unary(x->data, x->dtype, out->data, op, x->ne, ctx->stream, lo, hi);
     return out;
 }
 
@@ -438,6 +446,171 @@ extern "C" dsc_tensor *dsc_real(dsc_ctx *ctx, dsc_tensor *x) {
 extern "C" dsc_tensor *dsc_imag(dsc_ctx *ctx, const dsc_tensor *x) {
     DSC_ASSERT(x != nullptr);
     return unary_entry(ctx, x, nullptr, 4, as_real(x->dtype));
+}
+
+// ------------------------------------------------------------------------------ transcendental unary, i0, clip
+
+// dsc.cpp:1348-1443 (validate_unary_params, dsc.cpp:71-81): out == NULL allocates a tensor like x, otherwise out must have
+// x's dtype and shape; the result keeps x's dtype
+#define DSC_UNARY_SAME_DTYPE(name_, op_)                                                       \
+    extern "C" dsc_tensor *name_(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out) {        \
+        DSC_ASSERT(x != nullptr);                                                              \
+        return unary_entry(ctx, x, out, (op_), x->dtype);                                      \
+    }
+DSC_UNARY_SAME_DTYPE(dsc_cos, 5)
+DSC_UNARY_SAME_DTYPE(dsc_sin, 6)
+DSC_UNARY_SAME_DTYPE(dsc_sinc, 7)
+DSC_UNARY_SAME_DTYPE(dsc_logn, 8)
+DSC_UNARY_SAME_DTYPE(dsc_log2, 9)
+DSC_UNARY_SAME_DTYPE(dsc_log10, 10)
+DSC_UNARY_SAME_DTYPE(dsc_exp, 11)
+DSC_UNARY_SAME_DTYPE(dsc_sqrt, 12)
+#undef DSC_UNARY_SAME_DTYPE
+
+// dsc.cpp:1701-1722 (i0 itself :1625-1687): real tensors only, always a new tensor
+extern "C" dsc_tensor *dsc_i0(dsc_ctx *ctx, const dsc_tensor *x) {
+    DSC_ASSERT(x != nullptr);
+    DSC_ASSERT(x->dtype == DSC_F32 || x->dtype == DSC_F64);
+    return unary_entry(ctx, x, nullptr, 13, x->dtype);
+}
+
+// dsc.cpp:1724-1770: out = min_op(max_op(x, x_min), x_max); the bounds are cast to the tensor's real type
+extern "C" dsc_tensor *dsc_clip(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, double x_min, double x_max) {
+    DSC_ASSERT(x != nullptr);
+    return unary_entry(ctx, x, out, 14, x->dtype, x_min, x_max);
+}
+
+// ------------------------------------------------------------------------------ creation, reshape, concat
+
+// dsc.cpp:477-499: [0, 1, .., n - 1] by a running sum in the dtype, made on the device
+extern "C" dsc_tensor *dsc_arange(dsc_ctx *ctx, int n, dsc_dtype dtype) {
+    DSC_TRACE_OP(ctx, "op;creation", nullptr, nullptr, n, (int) dtype);
+    DSC_ASSERT(dtype < 4);
+    dsc_tensor *out = dsc_tensor_1d(ctx, dtype, n);
+    dsc_launch_arange(out->data, dtype, out->ne, ctx->stream);
+    return out;
+}
+
+// dsc.cpp:501-534 (dsc_fill_randn + dsc_randn): the reference default-constructs std::mt19937 and std::normal_distribution<T>
+// on every call, so every call yields the same fixed sequence.  The one operator whose values are made on the host: the same
+// libstdc++ types generate them here (bit-exact parity with the reference) and one copy places them in HBM.  The f64 generator
+// lives in randn_host.cpp, compiled with the reference build's FMA contraction.
+void dsc_randn_host_f64(double *dst, size_t n);
+
+static void randn_host_f32(float *dst, size_t n) {
+    std::mt19937 rng;
+    std::normal_distribution<float> dist;
+    for (size_t i = 0; i < n; ++i) dst[i] = dist(rng);
+}
+
+template<typename T>
+static void fill_randn(dsc_ctx *ctx, dsc_tensor *out) {
+    std::vector<T> host((size_t) out->ne);
+    if constexpr (sizeof(T) == 4) randn_host_f32(host.data(), host.size());
+    else                          dsc_randn_host_f64(host.data(), host.size());
+    dsc_copy_from_host(ctx, out, host.data(), host.size() * sizeof(T));
+}
+
+extern "C" dsc_tensor *dsc_randn(dsc_ctx *ctx, int n_dim, const int *shape, dsc_dtype dtype) {
+    DSC_TRACE_OP(ctx, "op;creation", nullptr, nullptr, n_dim, (int) dtype);
+    DSC_ASSERT(shape != nullptr);
+    if (dtype != DSC_F32 && dtype != DSC_F64) DSC_LOG_FATAL("dtype must be real");
+    dsc_tensor *out = dsc_new_tensor(ctx, n_dim, shape, dtype, nullptr);
+    if (dtype == DSC_F32) fill_randn<float>(ctx, out);
+    else                  fill_randn<double>(ctx, out);
+    return out;
+}
+
+// dsc.cpp:599-636: a new header over x's buffer (shared, refcounted as dsc_view); at most one negative ("unknown") dimension,
+// inferred from the element count; any other mismatch is fatal
+extern "C" dsc_tensor *dsc_reshape(dsc_ctx *ctx, const dsc_tensor *x, int dimensions, ...) {
+    DSC_ASSERT(x != nullptr);
+    DSC_ASSERT((unsigned) dimensions <= DSC_MAX_DIMS);
+    DSC_TRACE_OP(ctx, "op;reshape", x, nullptr, dimensions, 0);
+    int new_shape[DSC_MAX_DIMS] = {1, 1, 1, 1};
+    long long new_ne = 1;
+    int unknown_dim = -1;
+    va_list args;
+    va_start(args, dimensions);
+    for (int i = 0; i < dimensions; ++i) {
+        const int el = va_arg(args, int);
+        if (el < 0) {
+            if (unknown_dim == -1) unknown_dim = i;
+            else { va_end(args); DSC_LOG_FATAL("can only specify one unknown dim"); }
+        } else {
+            new_ne *= el;
+            new_shape[i] = el;
+        }
+    }
+    va_end(args);
+    if (unknown_dim != -1) {
+        if (new_ne == 0 || x->ne % new_ne != 0) DSC_LOG_FATAL("cannot reshape %d into %lld with an unknown dimension", x->ne, new_ne);
+        new_shape[unknown_dim] = (int) (x->ne / new_ne);
+        new_ne = x->ne;
+    }
+    DSC_ASSERT(x->ne == new_ne);
+    return dsc_new_tensor(ctx, dimensions, new_shape, x->dtype, x->buffer);
+}
+
+// dsc.cpp:665-740: the inputs (same dtype, same n_dim, equal extents off the axis) side by side along `axis`; DSC_VALUE_NONE
+// flattens them into one 1-D tensor.  On the device: one stream-ordered copy per input — a D2D memcpy when flattening, else a
+// scatter of the dense input into its strided block of the output (the slice kernels, dsc_launch_region_copy).
+extern "C" dsc_tensor *dsc_concat(dsc_ctx *ctx, int axis, int tensors, ...) {
+    DSC_ASSERT(tensors > 1);
+    DSC_TRACE_OP(ctx, "op;concat", nullptr, nullptr, tensors, axis);
+    std::vector<dsc_tensor *> xs((size_t) tensors);
+    va_list args;
+    va_start(args, tensors);
+    for (int i = 0; i < tensors; ++i) xs[i] = va_arg(args, dsc_tensor *);
+    va_end(args);
+    for (dsc_tensor *t : xs) DSC_ASSERT(t != nullptr);
+    const dsc_dtype dtype = xs[0]->dtype;
+    const int n_dim = xs[0]->n_dim;
+    for (int i = 1; i < tensors; ++i) {
+        DSC_ASSERT(xs[i]->dtype == dtype);
+        DSC_ASSERT(xs[i]->n_dim == n_dim);
+    }
+    const size_t esz = dsc_dtype_size(dtype);
+
+    if (axis == DSC_VALUE_NONE) {
+        long long ne = 0;
+        for (dsc_tensor *t : xs) ne += t->ne;
+        DSC_ASSERT(ne <= 0x7fffffffLL);
+        dsc_tensor *out = dsc_tensor_1d(ctx, dtype, (int) ne);
+        size_t offset = 0;
+        for (dsc_tensor *t : xs) {
+            const size_t nb = (size_t) t->ne * esz;
+            HIP_CHECK(hipMemcpyAsync((char *) out->data + offset, t->data, nb, hipMemcpyDeviceToDevice, ctx->stream));
+            offset += nb;
+        }
+        return out;
+    }
+
+    const int slot = dsc_axis_slot(xs[0], axis);
+    DSC_ASSERT(slot >= DSC_MAX_DIMS - n_dim && slot < DSC_MAX_DIMS);
+    int shape[DSC_MAX_DIMS];
+    memcpy(shape, xs[0]->shape, sizeof(shape));
+    long long axis_total = shape[slot];
+    for (int i = 1; i < tensors; ++i) {
+        for (int d = 0; d < DSC_MAX_DIMS; ++d) {
+            if (d == slot) axis_total += xs[i]->shape[d];
+            else DSC_ASSERT(xs[i]->shape[d] == xs[0]->shape[d]);
+        }
+    }
+    DSC_ASSERT(axis_total <= 0x7fffffffLL);
+    shape[slot] = (int) axis_total;
+    dsc_tensor *out = dsc_new_tensor(ctx, n_dim, &shape[DSC_MAX_DIMS - n_dim], dtype, nullptr);
+
+    long long at = 0;                     // where the current input starts along the axis
+    for (dsc_tensor *t : xs) {
+        dsc_region r;
+        r.base = at * out->stride[slot];
+        r.ne = t->ne;
+        for (int d = 0; d < DSC_MAX_DIMS; ++d) { r.count[d] = t->shape[d]; r.stride[d] = out->stride[d]; }
+        dsc_launch_region_copy(t->data, out->data, (int) esz, r, true, t->ne, ctx->stream);
+        at += t->shape[slot];
+    }
+    return out;
 }
 
 // ------------------------------------------------------------------------------ reductions

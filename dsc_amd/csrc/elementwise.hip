@@ -103,22 +103,79 @@ void cast_from(const void *in, void *out, int out_dtype, long long ne, dim3, hip
     }
 }
 
-// add_op / sub_op / mul_op / div_op: dsc_ops.h:46-90
+// ---- transcendental functions of dsc_ops.h:92-229, generic over the four element types.  Real parts go to ocml's ACCURATE
+// functions (sinf / sin, expf / exp, ...; never the __sinf-style intrinsics); complex values use the reference's own formulas
+// (cos z = (cos a cosh b, -sin a sinh b), ...), not std::complex or ocml's complex functions.
+__device__ __forceinline__ float  m_sin(float x)             { return sinf(x); }
+__device__ __forceinline__ double m_sin(double x)            { return sin(x); }
+__device__ __forceinline__ float  m_cos(float x)             { return cosf(x); }
+__device__ __forceinline__ double m_cos(double x)            { return cos(x); }
+__device__ __forceinline__ float  m_sinh(float x)            { return sinhf(x); }
+__device__ __forceinline__ double m_sinh(double x)           { return sinh(x); }
+__device__ __forceinline__ float  m_cosh(float x)            { return coshf(x); }
+__device__ __forceinline__ double m_cosh(double x)           { return cosh(x); }
+__device__ __forceinline__ float  m_exp(float x)             { return expf(x); }
+__device__ __forceinline__ double m_exp(double x)            { return exp(x); }
+__device__ __forceinline__ float  m_log(float x)             { return logf(x); }
+__device__ __forceinline__ double m_log(double x)            { return log(x); }
+__device__ __forceinline__ float  m_log2(float x)            { return log2f(x); }
+__device__ __forceinline__ double m_log2(double x)           { return log2(x); }
+__device__ __forceinline__ float  m_log10(float x)           { return log10f(x); }
+__device__ __forceinline__ double m_log10(double x)          { return log10(x); }
+__device__ __forceinline__ float  m_sqrt(float x)            { return sqrtf(x); }
+__device__ __forceinline__ double m_sqrt(double x)           { return sqrt(x); }
+__device__ __forceinline__ float  m_atan2(float y, float x)  { return atan2f(y, x); }
+__device__ __forceinline__ double m_atan2(double y, double x) { return atan2(y, x); }
+__device__ __forceinline__ float  m_pow(float a, float b)    { return powf(a, b); }
+__device__ __forceinline__ double m_pow(double a, double b)  { return pow(a, b); }
+
+// exp_op (dsc_ops.h:211-227)
+template<typename T>
+__device__ __forceinline__ T t_exp(T v) {
+    if constexpr (elem<T>::cplx) {
+        const auto f = m_exp(v.x);
+        return T{f * m_cos(v.y), f * m_sin(v.y)};
+    } else {
+        return m_exp(v);
+    }
+}
+
+// logn_op / log2_op / log10_op (dsc_ops.h:144-191), BASE 0 = e: complex log = (log_B sqrt(re^2 + im^2), atan2(im, re) / ln B);
+// the factor is the reference's 1 / log(B) rounded to the real type
+template<typename T, int BASE>
+__device__ __forceinline__ T t_log(T v) {
+    using R = typename elem<T>::real;
+    auto lg = [](R x) { return BASE == 0 ? m_log(x) : BASE == 2 ? m_log2(x) : m_log10(x); };
+    if constexpr (elem<T>::cplx) {
+        const R fact = BASE == 0 ? (R) 1 : BASE == 2 ? (R) 1 / (R) 0.693147180559945309417232121458176568
+                                                      : (R) 1 / (R) 2.302585092994045684017991454684364208;
+        const R phase = m_atan2(v.y, v.x);
+        return T{lg(m_sqrt((v.x * v.x) + (v.y * v.y))), BASE == 0 ? phase : fact * phase};
+    } else {
+        return lg(v);
+    }
+}
+
+// add_op / sub_op / mul_op / div_op: dsc_ops.h:46-90; OP 4 = pow_op (dsc_ops.h:305-316): pow / powf on reals,
+// exp(b * log a) on complex values — the reference's own composition of exp_op, mul_op and logn_op
 template<typename T, int OP>
 __device__ __forceinline__ T apply(T a, T b) {
     if constexpr (elem<T>::cplx) {
         if constexpr (OP == 0) return T{a.x + b.x, a.y + b.y};
         else if constexpr (OP == 1) return T{a.x - b.x, a.y - b.y};
         else if constexpr (OP == 2) return T{(a.x * b.x) - (a.y * b.y), (a.x * b.y) + (a.y * b.x)};
-        else {
+        else if constexpr (OP == 3) {
             const auto den = (b.x * b.x) + (b.y * b.y);
             return T{((a.x * b.x) + (a.y * b.y)) / den, ((a.y * b.x) - (a.x * b.y)) / den};
+        } else {
+            return t_exp(apply<T, 2>(b, t_log<T, 0>(a)));
         }
     } else {
         if constexpr (OP == 0) return a + b;
         else if constexpr (OP == 1) return a - b;
         else if constexpr (OP == 2) return a * b;
-        else return a / b;
+        else if constexpr (OP == 3) return a / b;
+        else return m_pow(a, b);
     }
 }
 
@@ -320,7 +377,8 @@ bool binary_bcast_pack(const T *pa, const T *pb, T *po, int op, const dsc_bcast_
         case 0: DSC_LAUNCH((binary_bcast_pack_kernel<T, 0>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
         case 1: DSC_LAUNCH((binary_bcast_pack_kernel<T, 1>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
         case 2: DSC_LAUNCH((binary_bcast_pack_kernel<T, 2>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
-        default: DSC_LAUNCH((binary_bcast_pack_kernel<T, 3>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
+        case 3: DSC_LAUNCH((binary_bcast_pack_kernel<T, 3>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
+        default: DSC_LAUNCH((binary_bcast_pack_kernel<T, 4>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
     }
     return true;
 }
@@ -333,6 +391,7 @@ void binary_typed(const void *a, const void *b, void *out, int op, const dsc_bca
     if (op == 1 && binary_fast<T, 1>(pa, pb, po, g, grid, s)) return;
     if (op == 2 && binary_fast<T, 2>(pa, pb, po, g, grid, s)) return;
     if (op == 3 && binary_fast<T, 3>(pa, pb, po, g, grid, s)) return;
+    if (op == 4 && binary_fast<T, 4>(pa, pb, po, g, grid, s)) return;
     if (binary_bcast_pack<T>(pa, pb, po, op, g, s)) return;
     const long long rows = g.out_shape[3] > 0 ? g.ne / g.out_shape[3] : 0;
     const unsigned chunks = (unsigned) ((g.out_shape[3] + 1023) / 1024);
@@ -342,7 +401,8 @@ void binary_typed(const void *a, const void *b, void *out, int op, const dsc_bca
             case 0: DSC_LAUNCH((binary_rows_kernel<T, 0>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
             case 1: DSC_LAUNCH((binary_rows_kernel<T, 1>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
             case 2: DSC_LAUNCH((binary_rows_kernel<T, 2>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
-            default: DSC_LAUNCH((binary_rows_kernel<T, 3>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
+            case 3: DSC_LAUNCH((binary_rows_kernel<T, 3>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
+            default: DSC_LAUNCH((binary_rows_kernel<T, 4>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
         }
         return;
     }
@@ -350,45 +410,109 @@ void binary_typed(const void *a, const void *b, void *out, int op, const dsc_bca
         case 0: DSC_LAUNCH((binary_kernel<T, 0>), grid, dim3(256), 0, s, pa, pb, po, g); break;
         case 1: DSC_LAUNCH((binary_kernel<T, 1>), grid, dim3(256), 0, s, pa, pb, po, g); break;
         case 2: DSC_LAUNCH((binary_kernel<T, 2>), grid, dim3(256), 0, s, pa, pb, po, g); break;
-        default: DSC_LAUNCH((binary_kernel<T, 3>), grid, dim3(256), 0, s, pa, pb, po, g); break;
+        case 3: DSC_LAUNCH((binary_kernel<T, 3>), grid, dim3(256), 0, s, pa, pb, po, g); break;
+        default: DSC_LAUNCH((binary_kernel<T, 4>), grid, dim3(256), 0, s, pa, pb, po, g); break;
     }
 }
 
 // abs / angle / conj / real / imag: dsc/src/dsc.cpp:1480-1622, functors dsc_ops.h:242-303.
 // OP: 0 abs, 1 angle, 2 conj, 3 real, 4 imag.  Tin real or complex, output real (conj: same as input).
-template<typename Tin, int OP> struct unary_out { using type = typename elem<Tin>::real; };
+// OP 5 .. 14 keep the input's dtype (dsc.cpp:1299-1440, 1640-1770; dsc_ops.h:92-229, 318-339):
+//   5 cos, 6 sin, 7 sinc, 8 logn, 9 log2, 10 log10, 11 exp, 12 sqrt, 13 i0 (real only), 14 clip(lo, hi)
+template<typename Tin, int OP> struct unary_out { using type = typename std::conditional<(OP >= 5), Tin, typename elem<Tin>::real>::type; };
 template<typename R> struct unary_out<cx<R>, 2> { using type = cx<R>; };
 
+struct unary_params { double lo, hi; };     // clip bounds (f64 in the ABI, cast to the tensor's real type as dsc.cpp:1740-1765)
+
+// Modified Bessel function I0, Abramowitz & Stegun 9.8.1 (|x| < 3.75, t = x / 3.75) and 9.8.2 (|x| >= 3.75): the two
+// polynomial approximations the reference evaluates (dsc.cpp:1625-1687), in the real type of the tensor.
+template<typename R>
+__device__ __forceinline__ R bessel_i0(R x) {
+    const R ax = x >= 0 ? x : -x;
+    if (ax < (R) 3.75) {
+        R y = x / (R) 3.75;
+        y *= y;
+        return (R) 1 + y * ((R) 3.5156229 + y * ((R) 3.0899424 + y * ((R) 1.2067492 + y * ((R) 0.2659732 + y * ((R) 0.360768e-1 + y * (R) 0.45813e-2)))));
+    }
+    const R y = (R) 3.75 / ax;
+    return (m_exp(ax) / m_sqrt(ax)) *
+           ((R) 0.39894228 + y * ((R) 0.1328592e-1 + y * ((R) 0.225319e-2 + y * ((R) -0.157565e-2 + y * ((R) 0.916281e-2 +
+            y * ((R) -0.2057706e-1 + y * ((R) 0.2635537e-1 + y * ((R) -0.1647633e-1 + y * (R) 0.392377e-2))))))));
+}
+
 template<typename Tin, int OP>
-__device__ __forceinline__ typename unary_out<Tin, OP>::type unary_one(Tin v) {
+__device__ __forceinline__ typename unary_out<Tin, OP>::type unary_one(Tin v, const unary_params p) {
     using R = typename elem<Tin>::real;
+    constexpr bool C = elem<Tin>::cplx;
     R re, im;
-    if constexpr (elem<Tin>::cplx) { re = v.x; im = v.y; }
-    else                           { re = v; im = (R) 0; }
+    if constexpr (C) { re = v.x; im = v.y; }
+    else             { re = v; im = (R) 0; }
     if constexpr (OP == 0) {
-        if constexpr (elem<Tin>::cplx) return sqrt((re * re) + (im * im));
-        else                           return re >= 0 ? re : -re;
+        if constexpr (C) return sqrt((re * re) + (im * im));
+        else             return re >= 0 ? re : -re;
     } else if constexpr (OP == 1) {
         return atan2(im, re);
     } else if constexpr (OP == 2) {
-        if constexpr (elem<Tin>::cplx) return Tin{re, -im};
-        else                           return re;
+        if constexpr (C) return Tin{re, -im};
+        else             return re;
     } else if constexpr (OP == 3) {
         return re;
-    } else {
+    } else if constexpr (OP == 4) {
         return im;
+    } else if constexpr (OP == 5) {                                       // cos_op
+        if constexpr (C) return Tin{m_cos(re) * m_cosh(im), -m_sin(re) * m_sinh(im)};
+        else             return m_cos(re);
+    } else if constexpr (OP == 6 || OP == 7) {                            // sin_op; sinc_op = sin(pi x) / (pi x), 1 at 0
+        constexpr R pi = (R) 3.14159265358979323846;
+        const R a = OP == 7 ? pi * re : re, b = OP == 7 ? pi * im : im;
+        if constexpr (C) {
+            const Tin s{m_sin(a) * m_cosh(b), m_cos(a) * m_sinh(b)};
+            if constexpr (OP == 6) return s;
+            else return (re == (R) 0 && im == (R) 0) ? Tin{(R) 1, (R) 0} : apply<Tin, 3>(s, Tin{a, b});   // through div_op
+        } else {
+            if constexpr (OP == 6) return m_sin(a);
+            else return re == (R) 0 ? (R) 1 : m_sin(a) / a;
+        }
+    } else if constexpr (OP == 8) {
+        return t_log<Tin, 0>(v);
+    } else if constexpr (OP == 9) {
+        return t_log<Tin, 2>(v);
+    } else if constexpr (OP == 10) {
+        return t_log<Tin, 10>(v);
+    } else if constexpr (OP == 11) {
+        return t_exp(v);
+    } else if constexpr (OP == 12) {                                      // sqrt_op: the sign of the imaginary part from im >= 0
+        if constexpr (C) {
+            const R abs = m_sqrt((re * re) + (im * im));
+            const R sign = im >= 0 ? (R) 1 : (R) -1;
+            return Tin{m_sqrt((R) 0.5 * (abs + re)), sign * m_sqrt((R) 0.5 * (abs - re))};
+        } else {
+            return m_sqrt(re);
+        }
+    } else if constexpr (OP == 13) {
+        static_assert(!C, "i0 is real only");
+        return bessel_i0(re);
+    } else {                                                              // clip: min_op(max_op(x, lo), hi)
+        const R lo = (R) p.lo, hi = (R) p.hi;
+        if constexpr (C) {                                                // compare real parts; a bound comes back as (bound, 0)
+            const Tin m = re > lo ? v : Tin{lo, (R) 0};
+            return m.x > hi ? Tin{hi, (R) 0} : m;
+        } else {                                                          // DSC_MAX / DSC_MIN (dsc.h:43-44): NaN -> lo
+            const R m = re > lo ? re : lo;
+            return m < hi ? m : hi;
+        }
     }
 }
 
 template<typename Tin, int OP>
-__global__ void unary_kernel(const Tin *in, void *out, long long ne) {
+__global__ void unary_kernel(const Tin *in, void *out, long long ne, const unary_params p) {
     using Tout = typename unary_out<Tin, OP>::type;
     for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < ne; i += (long long) gridDim.x * blockDim.x)
-        ((Tout *) out)[i] = unary_one<Tin, OP>(in[i]);
+        ((Tout *) out)[i] = unary_one<Tin, OP>(in[i], p);
 }
 
 template<typename Tin, int OP, int V>
-__global__ void unary_pack_kernel(const Tin *in, void *out, unsigned npack) {
+__global__ void unary_pack_kernel(const Tin *in, void *out, unsigned npack, const unary_params p) {
     using Tout = typename unary_out<Tin, OP>::type;
     const packed<Tin, V> *pi = (const packed<Tin, V> *) in;
     packed<Tout, V> *po = (packed<Tout, V> *) out;
@@ -396,36 +520,90 @@ __global__ void unary_pack_kernel(const Tin *in, void *out, unsigned npack) {
         const packed<Tin, V> x = pi[i];
         packed<Tout, V> r;
 #pragma unroll
-        for (int j = 0; j < V; ++j) r.e[j] = unary_one<Tin, OP>(x.e[j]);
+        for (int j = 0; j < V; ++j) r.e[j] = unary_one<Tin, OP>(x.e[j], p);
         po[i] = r;
     }
 }
 
 template<typename Tin, int OP>
-void unary_op(const Tin *x, void *out, long long ne, hipStream_t s) {
+void unary_op(const Tin *x, void *out, long long ne, const unary_params p, hipStream_t s) {
     using Tout = typename unary_out<Tin, OP>::type;
     constexpr int V = pack_width<Tin, Tout>();
     long long done = 0;
     if (V > 1 && ne >= V && aligned_to(x, sizeof(Tin) * V) && aligned_to(out, sizeof(Tout) * V)) {
         const long long npack = ne / V;
-        DSC_LAUNCH((unary_pack_kernel<Tin, OP, V>), pack_grid(npack), dim3(256), 0, s, x, out, (unsigned) npack);
+        DSC_LAUNCH((unary_pack_kernel<Tin, OP, V>), pack_grid(npack), dim3(256), 0, s, x, out, (unsigned) npack, p);
         done = npack * V;
     }
     if (done < ne) {
-        if (V == 1) DSC_LAUNCH((unary_kernel<Tin, OP>), pack_grid(ne), dim3(256), 0, s, x, out, ne);       // 16 bytes per element already
-        else DSC_LAUNCH((unary_kernel<Tin, OP>), stream_grid(ne - done), dim3(256), 0, s, x + done, (void *) ((Tout *) out + done), ne - done);
+        if (V == 1) DSC_LAUNCH((unary_kernel<Tin, OP>), pack_grid(ne), dim3(256), 0, s, x, out, ne, p);       // 16 bytes per element already
+        else DSC_LAUNCH((unary_kernel<Tin, OP>), stream_grid(ne - done), dim3(256), 0, s, x + done, (void *) ((Tout *) out + done), ne - done, p);
     }
 }
 
 template<typename Tin>
-void unary_typed(const void *in, void *out, int op, long long ne, dim3, hipStream_t s) {
+void unary_typed(const void *in, void *out, int op, long long ne, const unary_params p, hipStream_t s) {
     const Tin *x = (const Tin *) in;
     switch (op) {
-        case 0: unary_op<Tin, 0>(x, out, ne, s); break;
-        case 1: unary_op<Tin, 1>(x, out, ne, s); break;
-        case 2: unary_op<Tin, 2>(x, out, ne, s); break;
-        case 3: unary_op<Tin, 3>(x, out, ne, s); break;
-        default: unary_op<Tin, 4>(x, out, ne, s); break;
+        case 0: unary_op<Tin, 0>(x, out, ne, p, s); break;
+        case 1: unary_op<Tin, 1>(x, out, ne, p, s); break;
+        case 2: unary_op<Tin, 2>(x, out, ne, p, s); break;
+        case 3: unary_op<Tin, 3>(x, out, ne, p, s); break;
+        case 4: unary_op<Tin, 4>(x, out, ne, p, s); break;
+        case 5: unary_op<Tin, 5>(x, out, ne, p, s); break;
+        case 6: unary_op<Tin, 6>(x, out, ne, p, s); break;
+        case 7: unary_op<Tin, 7>(x, out, ne, p, s); break;
+        case 8: unary_op<Tin, 8>(x, out, ne, p, s); break;
+        case 9: unary_op<Tin, 9>(x, out, ne, p, s); break;
+        case 10: unary_op<Tin, 10>(x, out, ne, p, s); break;
+        case 11: unary_op<Tin, 11>(x, out, ne, p, s); break;
+        case 12: unary_op<Tin, 12>(x, out, ne, p, s); break;
+        case 13:
+            if constexpr (!elem<Tin>::cplx) { unary_op<Tin, 13>(x, out, ne, p, s); break; }
+            fprintf(stderr, "dsc_launch_unary: i0 of a complex tensor\n");
+            exit(EXIT_FAILURE);
+        case 14: unary_op<Tin, 14>(x, out, ne, p, s); break;
+        default:
+            fprintf(stderr, "dsc_launch_unary: unknown op %d\n", op);
+            exit(EXIT_FAILURE);
+    }
+}
+
+// arange (dsc.cpp:430-439, 477-499): the reference accumulates val += 1 in T, so an f32 (or c32 real part) saturates at
+// 2^24 — 2^24 + 1 rounds back to 2^24 — and element i is min(i, 2^24); f64 is exact for every int n.
+template<typename T>
+__device__ __forceinline__ T arange_value(long long i) {
+    using R = typename elem<T>::real;
+    const R v = sizeof(R) == 4 ? (R) (i < (1LL << 24) ? i : (1LL << 24)) : (R) i;
+    if constexpr (elem<T>::cplx) return T{v, (R) 0};
+    else                         return v;
+}
+
+// one pack of V elements per thread (16-byte stores), the elements past n of the last pack written one by one
+template<typename T, int V>
+__global__ void arange_kernel(T *out, unsigned npack, long long n) {
+    packed<T, V> *po = (packed<T, V> *) out;
+    for (unsigned p = blockIdx.x * blockDim.x + threadIdx.x; p < npack; p += gridDim.x * blockDim.x) {
+        const long long e0 = (long long) p * V;
+        if (e0 + V <= n) {
+            packed<T, V> r;
+#pragma unroll
+            for (int j = 0; j < V; ++j) r.e[j] = arange_value<T>(e0 + j);
+            po[p] = r;
+        } else {
+            for (long long e = e0; e < n; ++e) out[e] = arange_value<T>(e);
+        }
+    }
+}
+
+template<typename T>
+void arange_typed(void *out, long long n, hipStream_t s) {
+    constexpr int V = 16 / sizeof(T);
+    if (aligned_to(out, 16)) {
+        const long long npack = (n + V - 1) / V;
+        DSC_LAUNCH((arange_kernel<T, V>), pack_grid(npack), dim3(256), 0, s, (T *) out, (unsigned) npack, n);
+    } else {
+        DSC_LAUNCH((arange_kernel<T, 1>), pack_grid(n), dim3(256), 0, s, (T *) out, (unsigned) n, n);
     }
 }
 
@@ -442,14 +620,24 @@ void dsc_launch_cast(const void *in, int in_dtype, void *out, int out_dtype, lon
     }
 }
 
-void dsc_launch_unary(const void *in, int in_dtype, void *out, int op, long long ne, hipStream_t stream) {
+void dsc_launch_unary(const void *in, int in_dtype, void *out, int op, long long ne, hipStream_t stream, double lo, double hi) {
     if (ne <= 0) return;
-    const dim3 grid = stream_grid(ne);
+    const unary_params p{lo, hi};
     switch (in_dtype) {
-        case 0: unary_typed<float>(in, out, op, ne, grid, stream); break;
-        case 1: unary_typed<double>(in, out, op, ne, grid, stream); break;
-        case 2: unary_typed<cx<float>>(in, out, op, ne, grid, stream); break;
-        default: unary_typed<cx<double>>(in, out, op, ne, grid, stream); break;
+        case 0: unary_typed<float>(in, out, op, ne, p, stream); break;
+        case 1: unary_typed<double>(in, out, op, ne, p, stream); break;
+        case 2: unary_typed<cx<float>>(in, out, op, ne, p, stream); break;
+        default: unary_typed<cx<double>>(in, out, op, ne, p, stream); break;
+    }
+}
+
+void dsc_launch_arange(void *out, int dtype, long long n, hipStream_t stream) {
+    if (n <= 0) return;
+    switch (dtype) {
+        case 0: arange_typed<float>(out, n, stream); break;
+        case 1: arange_typed<double>(out, n, stream); break;
+        case 2: arange_typed<cx<float>>(out, n, stream); break;
+        default: arange_typed<cx<double>>(out, n, stream); break;
     }
 }
 
@@ -492,7 +680,8 @@ bool mixed_pair(const void *a, const void *b, void *out, int op, long long ne, h
         case 0: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 0>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
         case 1: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 1>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
         case 2: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 2>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
-        default: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 3>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
+        case 3: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 3>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
+        default: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 4>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
     }
     return true;
 }

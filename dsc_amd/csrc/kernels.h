@@ -171,8 +171,11 @@ void dsc_launch_filter_regs_mid(const void *s, const void *H, void *y, long long
 // dtype codes are dsc_dtype values (0 f32, 1 f64, 2 c32, 3 c64)
 void dsc_launch_cast(const void *in, int in_dtype, void *out, int out_dtype, long long ne, hipStream_t stream);
 
-// op: 0 abs, 1 angle, 2 conj, 3 real, 4 imag (output real dtype of the input; conj keeps the dtype)
-void dsc_launch_unary(const void *in, int in_dtype, void *out, int op, long long ne, hipStream_t stream);
+// op: 0 abs, 1 angle, 2 conj, 3 real, 4 imag (output real dtype of the input; conj keeps the dtype);
+// 5 cos, 6 sin, 7 sinc, 8 logn, 9 log2, 10 log10, 11 exp, 12 sqrt, 13 i0 (f32 / f64 only), 14 clip to [lo, hi] (output dtype = input's)
+void dsc_launch_unary(const void *in, int in_dtype, void *out, int op, long long ne, hipStream_t stream, double lo = 0, double hi = 0);
+// out[i] = i in the dtype, saturating at 2^24 in f32 / c32 as the reference's running sum does
+void dsc_launch_arange(void *out, int dtype, long long n, hipStream_t stream);
 
 struct dsc_bcast_args {
     int out_shape[4];
@@ -186,7 +189,7 @@ struct dsc_bcast_args {
     int fast;
     int small_ne;             // fast = 2, 3: element count of the broadcast operand; fast = 4, 5: output elements per element of it
 };
-// op: 0 add, 1 sub, 2 mul, 3 div   (only mul is exported through the C ABI this round)
+// op: 0 add, 1 sub, 2 mul, 3 div, 4 pow
 void dsc_launch_binary(const void *a, const void *b, void *out, int dtype, int op, const dsc_bcast_args &g, hipStream_t stream);
 // operands of different dtypes, equal shapes, contiguous: casts to the promoted dtype in registers.  false = not taken
 // (odd element count or unaligned views): the caller casts into scratch tensors and calls dsc_launch_binary.

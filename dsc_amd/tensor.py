@@ -1,6 +1,6 @@
-"""`dsc.Tensor` and the hot-path operators (mirror of python/dsc/tensor.py for that subset:
-Tensor :159-331, from_numpy :371-377, mul :477-483, sum/mean/max/min :579-612,
-fft/ifft/rfft/irfft :693-726).
+"""`dsc.Tensor` and its operators (mirror of python/dsc/tensor.py: Tensor :159-331, from_numpy :371-377,
+reshape / concat :380-404, add .. power :459-501, cos .. sqrt :504-533, i0 / clip :560-576, sum/mean/max/min :579-612,
+arange / randn :615-620, fft/ifft/rfft/irfft :693-726).
 
 Differences forced by the device arena (see include/dsc_mi355x.h): `numpy()` and
 `from_numpy()` COPY through dsc_copy_to_host / dsc_copy_from_host instead of viewing /
@@ -93,6 +93,12 @@ class Tensor:
     def __rtruediv__(self, other):
         return true_div(other, self)
 
+    def __pow__(self, other):                                     # python/dsc/tensor.py:293-297
+        return power(self, other)
+
+    def __rpow__(self, other):
+        return power(other, self)
+
     def __getitem__(self, item):
         """python/dsc/tensor.py:193-229: ints -> dsc_tensor_get_idx (a fully indexed element is unwrapped to a
         Python scalar), slices or mixed -> dsc_tensor_get_slice.  The copy happens on the device."""
@@ -140,6 +146,9 @@ class Tensor:
         out_ptr = B.dsc_cast(_get_ctx(), self._c_ptr, dtype.value)
         same = B.ctypes.cast(out_ptr, B.c_void_p).value == B.ctypes.cast(self._c_ptr, B.c_void_p).value
         return Tensor(out_ptr, view=same)
+
+    def reshape(self, *shape) -> 'Tensor':                        # python/dsc/tensor.py:328-329
+        return reshape(self, *shape)
 
 
 def _unwrap(x: Tensor):
@@ -236,6 +245,10 @@ def true_div(xa, xb, out: Union[Tensor, None] = None) -> Tensor:    # :485-491
     return _binary(B.dsc_div, xa, xb, out)
 
 
+def power(xa, xb, out: Union[Tensor, None] = None) -> Tensor:       # :495-501
+    return _binary(B.dsc_pow, xa, xb, out)
+
+
 def _same_ptr(a, b) -> bool:
     return B.ctypes.cast(a, B.c_void_p).value == B.ctypes.cast(b, B.c_void_p).value
 
@@ -260,6 +273,79 @@ def real(x: Tensor) -> Tensor:                                            # :547
 
 def imag(x: Tensor) -> Tensor:                                            # :553-554
     return Tensor(B.dsc_imag(_get_ctx(), x._c_ptr))
+
+
+def _unary(f, x: Tensor, out) -> Tensor:
+    return Tensor(f(_get_ctx(), x._c_ptr, _c_ptr_or_none(out)), out is not None)
+
+
+def cos(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:            # python/dsc/tensor.py:504-533
+    return _unary(B.dsc_cos, x, out)
+
+
+def sin(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_sin, x, out)
+
+
+def sinc(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_sinc, x, out)
+
+
+def logn(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_logn, x, out)
+
+
+def log2(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_log2, x, out)
+
+
+def log10(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_log10, x, out)
+
+
+def exp(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_exp, x, out)
+
+
+def sqrt(x: Tensor, out: Union[Tensor, None] = None) -> Tensor:
+    return _unary(B.dsc_sqrt, x, out)
+
+
+def i0(x: Union[int, float, Tensor], dtype: Dtype = Dtype.F32) -> Tensor:       # :560-562: a Python scalar is wrapped first
+    x = _wrap(x, dtype)
+    return Tensor(B.dsc_i0(_get_ctx(), x._c_ptr))
+
+
+def clip(x: Tensor, x_min: Union[float, None] = None, x_max: Union[float, None] = None,
+         out: Union[Tensor, None] = None) -> Tensor:                                # :565-576: a missing bound is -inf / +inf
+    x_min = float(x_min) if x_min is not None else float('-inf')
+    x_max = float(x_max) if x_max is not None else float('+inf')
+    return Tensor(B.dsc_clip(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), x_min, x_max), out is not None)
+
+
+def arange(n: int, dtype: Dtype = Dtype.F32) -> Tensor:                  # :615-616
+    return Tensor(B.dsc_arange(_get_ctx(), n, dtype.value))
+
+
+def randn(*shape: int, dtype: Dtype = Dtype.F32) -> Tensor:              # :619-620
+    dims = (B.c_int * len(shape))(*shape)
+    return Tensor(B.dsc_randn(_get_ctx(), len(shape), dims, dtype.value))
+
+
+def reshape(x: Tensor, *shape) -> Tensor:                               # :380-391: ints, or one list / tuple of ints
+    if len(shape) == 1 and isinstance(shape[0], (tuple, list)) and all(isinstance(s, int) for s in shape[0]):
+        dims = tuple(shape[0])
+    elif all(isinstance(s, int) for s in shape):
+        dims = shape
+    else:
+        raise RuntimeError(f'cannot reshape tensor with shape {shape}')
+    return Tensor(B.dsc_reshape(_get_ctx(), x._c_ptr, *dims))
+
+
+def concat(tensors, axis: Union[int, None] = 0) -> Tensor:               # :394-404: axis=None flattens
+    if isinstance(tensors, (tuple, list)) and all(isinstance(t, Tensor) for t in tensors):
+        return Tensor(B.dsc_concat(_get_ctx(), axis if axis is not None else B.DSC_VALUE_NONE, *[t._c_ptr for t in tensors]))
+    raise RuntimeError(f'cannot concatenate tensors {tensors}')
 
 
 def _reduce(f, x: Tensor, out, axis: int, keepdims: bool) -> Tensor:

@@ -118,6 +118,18 @@ dsc_tensor *dsc_wrap_c64(dsc_ctx *ctx, dsc_c64 val);
 /* dsc.h:221-223, dsc.cpp:587-597: returns x itself when the dtype already matches. */
 dsc_tensor *dsc_cast(dsc_ctx *ctx, dsc_tensor *x, dsc_dtype new_dtype);
 
+/* dsc.h:212-219, dsc.cpp:477-534 — creation.  dsc_arange: [0, 1, .., n-1] as the reference's running sum in the dtype
+ * (f32 / c32 saturate at 2^24), made on the device.  dsc_randn: f32 / f64 only; every call returns the same fixed sequence,
+ * the reference's default-seeded std::mt19937 + std::normal_distribution, generated on the host and copied to HBM. */
+dsc_tensor *dsc_arange(dsc_ctx *ctx, int n, dsc_dtype dtype);
+dsc_tensor *dsc_randn(dsc_ctx *ctx, int n_dim, const int *shape, dsc_dtype dtype);
+
+/* dsc.h:225-232, dsc.cpp:599-740.  dsc_reshape: a view sharing x's buffer (and its refcount, as dsc_view); `dimensions` ints
+ * follow, at most one of them negative (inferred); a mismatched element count is fatal.  dsc_concat: `tensors` dsc_tensor*
+ * follow (same dtype and n_dim, equal extents off the axis); axis == DSC_VALUE_NONE flattens into a 1-D tensor. */
+dsc_tensor *dsc_reshape(dsc_ctx *ctx, const dsc_tensor *x, int dimensions, ...);
+dsc_tensor *dsc_concat(dsc_ctx *ctx, int axis, int tensors, ...);
+
 /* dsc.h:275-278, dsc.cpp:1273-1284 (+ :44-69, :1174-1245; dsc_ops.h:68-78).
  * NumPy-style broadcasting over the 4 right-aligned dims, result dtype from the
  * promotion table dsc_dtype.h:73-78 (F64 x C32 -> C32).  out may be NULL. */
@@ -127,6 +139,26 @@ dsc_tensor *dsc_mul(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *ou
 dsc_tensor *dsc_add(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out);
 dsc_tensor *dsc_sub(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out);
 dsc_tensor *dsc_div(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out);
+/* dsc.h:285-288, dsc.cpp:1299-1310 — pow_op (dsc_ops.h:305-316): pow on reals, exp(b log a) on complex values; the same
+ * broadcasting, promotion and result shape as dsc_add. */
+dsc_tensor *dsc_pow(dsc_ctx *ctx, dsc_tensor *xa, dsc_tensor *xb, dsc_tensor *out);
+
+/* dsc.h:293-323, dsc.cpp:1348-1443 (functors dsc_ops.h:92-229) — element-wise transcendental functions; the result has x's
+ * dtype (out may be NULL; if given it must match x's dtype and shape).  Complex values follow the reference's formulas. */
+dsc_tensor *dsc_cos(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_sin(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_sinc(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_logn(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_log2(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_log10(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_exp(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+dsc_tensor *dsc_sqrt(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out);
+
+/* dsc.h:342-353, dsc.cpp:1625-1770.  dsc_i0: modified Bessel function I0 of f32 / f64 tensors (Abramowitz & Stegun 9.8.1 /
+ * 9.8.2).  dsc_clip: min(max(x, x_min), x_max) with the reference's comparisons (NaN -> x_min; complex values compare by
+ * their real part and a bound comes back as (bound, 0)); pass -INFINITY / INFINITY for "no bound". */
+dsc_tensor *dsc_i0(dsc_ctx *ctx, const dsc_tensor *x);
+dsc_tensor *dsc_clip(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, double x_min, double x_max);
 
 /* dsc.h:325-340, dsc.cpp:1480-1622 (functors dsc_ops.h:242-303) — magnitude / phase / parts of a spectrum
  * (SURVEY 8f "next" row 2).  abs, angle, imag (and real of a complex tensor) return the REAL dtype of x;
