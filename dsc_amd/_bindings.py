@@ -168,6 +168,8 @@ dsc_timer_start = _sig('dsc_timer_start', None, _DscCtx)
 dsc_timer_stop = _sig('dsc_timer_stop', c_float, _DscCtx)
 dsc_filter_fft = _sig('dsc_filter_fft', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _DscTensor_p)
 dsc_last_fft_path = _sig('dsc_last_fft_path', c_char_p, _DscCtx)
+dsc_stft = _sig('dsc_stft', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p, c_bool, c_int, _DscTensor_p)
+dsc_istft = _sig('dsc_istft', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p, c_bool, c_int, _DscTensor_p)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

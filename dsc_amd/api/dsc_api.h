@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft` and `dsc::stft / istft`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -230,6 +230,17 @@ static inline tensor<T> concat(int axis, const tensor<T> &first, const Args &...
 // README.md:141-163 (C++ filterFFT) as one call: y = irfft(rfft(s, n) * H)
 template<typename T>
 static inline tensor<T> filter_fft(const tensor<T> &s, const tensor<T> &H) noexcept { return dsc_filter_fft(ctx, s.x_, H.x_, nullptr); }
+
+// Section D of dsc_mi355x.h: short-time transforms, frames-major spectrum [.., n_frames, n_fft/2 + 1] (complex payload, like rfft<T>);
+// window = nullptr: ones.  pad_mode 0 = reflect, 1 = zeros; length <= 0: the natural length.
+template<typename T>
+static inline tensor<T> stft(const tensor<T> &x, int n_fft, int hop, const tensor<T> *window = nullptr, bool center = true, int pad_mode = 0) noexcept {
+    return dsc_stft(ctx, x.x_, n_fft, hop, window ? window->x_ : nullptr, center, pad_mode, nullptr);
+}
+template<typename T>
+static inline tensor<T> istft(const tensor<T> &X, int n_fft, int hop, const tensor<T> *window = nullptr, bool center = true, int length = -1) noexcept {
+    return dsc_istft(ctx, X.x_, n_fft, hop, window ? window->x_ : nullptr, center, length, nullptr);
+}
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

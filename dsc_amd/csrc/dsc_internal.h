@@ -95,14 +95,18 @@ private:
 // in-order stream makes reuse after reset safe without waiting.
 class dsc_scratch_arena {
 public:
-    void init(char *base, size_t size) { base_ = base; size_ = size; top_ = 0; }
+    void init(char *base, size_t size) { base_ = base; size_ = size; top_ = 0; floor_ = 0; }
     char *alloc(size_t nb);
-    void reset() { top_ = 0; }
-    size_t capacity() const { return size_; }
+    void reset() { top_ = floor_; }
+    size_t capacity() const { return size_ - floor_; }
+    // pin(): what is allocated so far stays out of reach of reset() and capacity() — an operator holds a scratch block while it
+    // calls others that use the arena (dsc_stft / dsc_istft around the internal rfft / irfft routes); unpin() releases it all
+    void pin() { floor_ = top_; }
+    void unpin() { floor_ = 0; top_ = 0; }
 
 private:
     char *base_ = nullptr;
-    size_t size_ = 0, top_ = 0;
+    size_t size_ = 0, top_ = 0, floor_ = 0;
 };
 
 // Our buffer record: `pub.refs` first so that &rec->pub is the ABI's dsc_tensor_buffer*.

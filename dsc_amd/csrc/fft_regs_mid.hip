@@ -24,6 +24,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #include "fft_regs_common.h"
@@ -242,13 +243,54 @@ __device__ __forceinline__ void mid_passes(cpx<R> (&v)[32], R *plane, const cpx<
 
 }
 
+// Source of the lines.  no_frames: the lines of the input tensor.  stft_frames (dsc_stft, the fused forward route): line q = (row, frame)
+// of the packed-real transform reads the 2L samples x[row][frame * hop - pad + i], i < 2L, times w[i]; outside [0, T) a sample is
+// reflected (torch's 'reflect' padding: -i, 2 (T - 1) - i; the host guarantees pad < T) or reads zero.  Interior frames whose pairs are
+// 8-/16-byte aligned load them directly; edge frames and odd starts (odd hops) load the two samples of a pair one by one.
+struct no_frames {};
+__device__ __forceinline__ no_frames frames_of() { return no_frames{}; }
+template<typename F> __device__ __forceinline__ F frames_of(F f) { return f; }
+template<typename R> struct stft_frames {
+    const R *x;          // [rows][T], rows = n_lines / n_frames
+    const R *w;          // [2L] window, or NULL (ones)
+    int x_bytes;         // descriptor range of x; (rows + 1) T sizeof(R) + 2L sizeof(R) < 2^31 (host)
+    int T, n_frames, hop, pad;
+    int reflect;         // 1: reflect, 0: zeros
+};
+
+// byte offset of sample i (row coordinates, may lie outside [0, T)) of the row starting at element row_off, or an offset past any
+// descriptor range (reads zero)
+template<typename R>
+__device__ __forceinline__ int frame_sample_off(const stft_frames<R> &fr, int row_off, int i) {
+    if (fr.reflect) {
+        i = i < 0 ? -i : i;
+        i = i >= fr.T ? 2 * (fr.T - 1) - i : i;
+    }
+    return (unsigned) i < (unsigned) fr.T ? (row_off + i) * (int) sizeof(R) : 0x7f000000;
+}
+// samples s, s + 1 of the row as one packed-real input value, sample by sample
+template<int POL, typename R>
+__device__ __forceinline__ cpx<R> frame_pair_gather(const stft_frames<R> &fr, __amdgpu_buffer_rsrc_t rx, int row_off, int s) {
+    return cpx<R>{buf_load_real<POL>(rx, frame_sample_off(fr, row_off, s), 0, R{}).x,
+                  buf_load_real<POL>(rx, frame_sample_off(fr, row_off, s + 1), 0, R{}).x};
+}
+template<typename R>
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t window_rsrc(const stft_frames<R> &fr, int n) {
+    return __builtin_amdgcn_make_buffer_rsrc((void *) fr.w, 0, fr.w ? n * (int) sizeof(R) : 0, 0x00020000);
+}
+
 // MODE: DSC_MODE_C2C, DSC_MODE_R2C_CAST (L reals in), DSC_MODE_R2C_PACKED (forward only), DSC_MODE_C2R_PACKED (inverse only)
 // PAD: input lines have a pitch of in_pitch_b bytes and in_len_b valid bytes; the rest of the transform length reads as zero
 // (zero padding / cropping of dsc_fft / dsc_rfft / dsc_irfft with n != axis length, dsc.cpp:1990-1998, 2125-2133, 2149-2157).
-template<typename R, int B, bool TWO, int MODE, bool INV, bool PAD>
+// SRC: empty (the plain lines), or stft_frames<R> (MODE = R2C_PACKED, PAD = false; `in`, in_pitch_b and in_len_b unused).  An empty pack
+// leaves the kernel's signature and code as they are without frames.
+template<typename R, int B, bool TWO, int MODE, bool INV, bool PAD, typename... SRC>
 __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVES_PER_EU)) void fft_mid_kernel(
     const cpx<R> *__restrict__ in, cpx<R> *__restrict__ out, long long n_lines, const cpx<R> *__restrict__ tw_full,
-    const cpx<R> *__restrict__ tw_real, R scale, int in_pitch_b, int in_len_b) {
+    const cpx<R> *__restrict__ tw_real, R scale, int in_pitch_b, int in_len_b, SRC... frames) {
+    constexpr bool FRAMES = sizeof...(SRC) != 0;
+    static_assert(!FRAMES || (MODE == DSC_MODE_R2C_PACKED && !PAD), "frames feed the forward packed-real transform");
+    const auto fr = frames_of(frames...);
     using C = cpx<R>;
     using cfg = mid_cfg<R, B, TWO>;
     constexpr int T = cfg::T, L = cfg::L, G = cfg::G, NT = cfg::NT, SP = cfg::SP, CPT = cfg::CPT;
@@ -262,7 +304,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
     const int tid = threadIdx.x;
     const int g = T >= 64 ? __builtin_amdgcn_readfirstlane(tid / T) : tid / T;      // line within the group
     int t = tid - g * T;
-    constexpr bool PIPE = cfg::PIPE;
+    constexpr bool PIPE = cfg::PIPE && !FRAMES;                     // frames: every group takes G lines
     static_assert(!PIPE || G == 1, "the persistent form walks single lines");
     long long line0 = PIPE ? (long long) blockIdx.x : (long long) blockIdx.x * G;
     const long long left = n_lines - line0;
@@ -286,7 +328,8 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
     constexpr int STOREP = kComplex || (MODE == DSC_MODE_C2R_PACKED && !TWO) ? kStream : (cfg::PIPE && MODE == DSC_MODE_R2C_PACKED) ? DSC_MID_PIPE_REAL_STORE : kCached;
     const int pitch_b = PAD ? in_pitch_b : in_pitch * IB;
     auto in_rsrc = [&](long long first) {
-        return __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) in + first * pitch_b), 0,
+        if constexpr (FRAMES) return __builtin_amdgcn_make_buffer_rsrc((void *) fr.x, 0, fr.x_bytes, 0x00020000);
+        else return __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) in + first * pitch_b), 0,
                                                  PAD ? (n_valid - 1) * pitch_b + in_len_b : n_valid * in_pitch * IB, 0x00020000);
     };
     __amdgpu_buffer_rsrc_t rin = in_rsrc(line0);
@@ -312,6 +355,28 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
     for (int i = tid; i < cfg::TABLE; i += NT) wtab[i] = tw_full[(long long) i * cfg::TABLE_STRIDE];    // W_1024^m = W_L^{B m}
 
     C v[32];
+    if constexpr (FRAMES) {                                        // v[j1] = samples 2 (T j1 + t), + 1 of frame line0 + g, windowed
+        const long long line = line0 + g;
+        const int row = (int) (line / fr.n_frames);
+        const int row_off = row * fr.T, s0 = (int) (line - (long long) row * fr.n_frames) * fr.hop - fr.pad;
+        const bool direct = ((row_off + s0) & 1) == 0 && s0 >= 0 && s0 + 2 * L <= fr.T;
+        if (direct) {
+            const int vfr = (row_off + s0) * (int) sizeof(R) + t * CB;
+#pragma unroll
+            for (int j1 = 0; j1 < 32; ++j1) v[j1] = buf_load<LOADP>(rin, vfr, T * j1 * CB, R{});
+        } else {
+#pragma unroll
+            for (int j1 = 0; j1 < 32; ++j1) v[j1] = frame_pair_gather<LOADP>(fr, rin, row_off, s0 + 2 * (T * j1 + t));
+        }
+        if (fr.w != nullptr) {
+            const __amdgpu_buffer_rsrc_t rw = window_rsrc(fr, 2 * L);
+#pragma unroll
+            for (int j1 = 0; j1 < 32; ++j1) {
+                const C w = buf_load<kCached>(rw, t * CB, T * j1 * CB, R{});
+                v[j1] = C{v[j1].x * w.x, v[j1].y * w.y};
+            }
+        }
+    }
 #ifdef DSC_MID_OLD_PRE
     constexpr bool PRE_ONCE = false;
 #else
@@ -329,7 +394,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
     // two-pass lines (the same ownership: COLS = T CPT there too): f32 + 0.3 - 0.6 points, f64 no gain (tools/r03_call_r.sh)
     constexpr bool POST_ONCE = TWO ? (sizeof(R) == 4 && B > 1) : (sizeof(R) == 4 || B == 16);
 #endif
-    {
+    if constexpr (!FRAMES) {
 #pragma unroll
         for (int j1 = 0; j1 < 32; ++j1) v[j1] = load_elem(T * j1);                           // z[T j1 + t]
     }
@@ -794,10 +859,14 @@ template<typename R, int B, int MODE> constexpr size_t small_lds_bytes() { retur
 // PAD: the input lines have a pitch of in_pitch BYTES of which in_len BYTES are valid (a packed-real line may hold an odd number of
 // samples: the pair that straddles its end keeps the first sample only); the rest of the transform length reads as zero
 // (zero padding / cropping through n=, dsc.cpp:1990-1998, 2125-2133, 2149-2157) — e.g. frames of 200 samples transformed at 256.
-template<typename R, int B, int MODE, bool INV, bool PAD>
+// SRC: empty, or stft_frames<R> (MODE = R2C_PACKED, PAD = false; `in`, in_pitch and in_len unused): see fft_mid_kernel.
+template<typename R, int B, int MODE, bool INV, bool PAD, typename... SRC>
 __global__ __launch_bounds__((small_cfg<R, MODE>::NT)) void fft_small_kernel(const void *__restrict__ in, void *__restrict__ out, long long n_lines,
                                                                      const cpx<R> *__restrict__ tw_full, const cpx<R> *__restrict__ tw_real,
-                                                                     R scale, int in_pitch, int in_len) {
+                                                                     R scale, int in_pitch, int in_len, SRC... frames) {
+    constexpr bool FRAMES = sizeof...(SRC) != 0;
+    static_assert(!FRAMES || (MODE == DSC_MODE_R2C_PACKED && !PAD), "frames feed the forward packed-real transform");
+    const auto fr = frames_of(frames...);
     using C = cpx<R>;
     constexpr int NT = small_cfg<R, MODE>::NT, L = 32 * B, G = NT / B, P = 33 * B, LOGB = ilog2(B);
     constexpr bool REAL_IN = MODE == DSC_MODE_R2C_CAST;
@@ -822,11 +891,35 @@ __global__ __launch_bounds__((small_cfg<R, MODE>::NT)) void fft_small_kernel(con
     constexpr int CB = (int) sizeof(C), EB = REAL_IN ? (int) sizeof(R) : CB;
     constexpr int STEPS_IN = (G * IN_PITCH + NT - 1) / NT;                  // 32, or 33 for rows of L + 1 bins
     const long long gpitch_b = PAD ? (long long) in_pitch : (long long) IN_PITCH * EB;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) in + line0 * gpitch_b), 0,
-                                                                         (int) (PAD ? (n_valid - 1) * gpitch_b + in_len : n_valid * gpitch_b), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = [&] {
+        if constexpr (FRAMES) return __builtin_amdgcn_make_buffer_rsrc((void *) fr.x, 0, fr.x_bytes, 0x00020000);
+        else return __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) in + line0 * gpitch_b), 0,
+                                                      (int) (PAD ? (n_valid - 1) * gpitch_b + in_len : n_valid * gpitch_b), 0x00020000);
+    }();
     {
         C tmp[STEPS_IN];
-        if constexpr (PAD) {                                              // element (line, j) of the LDS image <- line * in_pitch + j, or zero
+        if constexpr (FRAMES) {                                           // element (line, j) of the LDS image <- samples 2j, 2j + 1 of frame line0 + line
+            static_assert(NT % IN_PITCH == 0 || IN_PITCH % NT == 0, "whole lines or whole steps");
+            int line = tid / IN_PITCH, j = tid % IN_PITCH;
+            const long long first = line0 + line;
+            int row = (int) (first / fr.n_frames), f = (int) (first - (long long) row * fr.n_frames);
+            const __amdgpu_buffer_rsrc_t rw = window_rsrc(fr, 2 * L);
+#pragma unroll
+            for (int m = 0; m < STEPS_IN; ++m) {
+                const int row_off = row * fr.T, s = f * fr.hop - fr.pad + 2 * j;
+                if (((row_off + s) & 1) == 0 && s >= 0 && s + 2 <= fr.T) tmp[m] = buf_load<kCached>(rin, (row_off + s) * (int) sizeof(R), 0, R{});
+                else                                                       tmp[m] = frame_pair_gather<kCached>(fr, rin, row_off, s);
+                if (fr.w != nullptr) {
+                    const C w = buf_load<kCached>(rw, j * CB, 0, R{});
+                    tmp[m] = C{tmp[m].x * w.x, tmp[m].y * w.y};
+                }
+                j += NT % IN_PITCH;
+                int dl = NT / IN_PITCH;
+                if (j >= IN_PITCH) { j -= IN_PITCH; ++dl; }
+                f += dl;
+                while (f >= fr.n_frames) { f -= fr.n_frames; ++row; }
+            }
+        } else if constexpr (PAD) {                                              // element (line, j) of the LDS image <- line * in_pitch + j, or zero
             int line = tid / IN_PITCH, j = tid % IN_PITCH;
 #pragma unroll
             for (int m = 0; m < STEPS_IN; ++m) {
@@ -1053,4 +1146,66 @@ void dsc_launch_filter_regs_mid(const void *s, const void *H, void *y, long long
     const int rb = single_precision ? 4 : 8;
     if (single_precision) launch_filter_len<float>(L, s, H, y, n_lines, tw_full, tw_real, (int) (in_pitch * rb), in_len * rb, stream);
     else                  launch_filter_len<double>(L, s, H, y, n_lines, tw_full, tw_real, (int) (in_pitch * rb), in_len * rb, stream);
+}
+
+namespace {
+
+template<typename R, int B, bool TWO>
+void launch_stft_mid(void *out, long long n_lines, const void *tw_full, const void *tw_real, const stft_frames<R> &fr, hipStream_t stream) {
+    using cfg = mid_cfg<R, B, TWO>;
+    constexpr size_t lds = mid_lds_bytes<R, B, TWO>();
+    static unsigned long long attr_devices = 0;
+    if (dsc_first_use_on_device(attr_devices)) {
+        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_kernel<R, B, TWO, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    }
+    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
+    DSC_LAUNCH((fft_mid_kernel<R, B, TWO, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, nullptr, (cpx<R> *) out, n_lines,
+               (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) 1, 0, 0, fr);
+}
+
+template<typename R, int B>
+void launch_stft_small(void *out, long long n_lines, const void *tw_full, const void *tw_real, const stft_frames<R> &fr, hipStream_t stream) {
+    constexpr int NT = small_cfg<R, DSC_MODE_R2C_PACKED>::NT, G = NT / B;
+    constexpr size_t lds = small_lds_bytes<R, B, DSC_MODE_R2C_PACKED>();
+    static unsigned long long attr_devices = 0;
+    if (dsc_first_use_on_device(attr_devices)) {
+        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_small_kernel<R, B, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    }
+    const long long groups = (n_lines + G - 1) / G;
+    DSC_LAUNCH((fft_small_kernel<R, B, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>), dim3((unsigned) groups), dim3(NT), lds, stream, nullptr, out, n_lines, (const cpx<R> *) tw_full,
+               (const cpx<R> *) tw_real, (R) 1, 0, 0, fr);
+}
+
+template<typename R>
+void launch_stft_len(int L, void *out, long long n_lines, const void *tw_full, const void *tw_real, const stft_frames<R> &fr, hipStream_t stream) {
+    switch (L) {
+        case 32:    launch_stft_small<R, 1>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 64:    launch_stft_small<R, 2>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 128:   launch_stft_small<R, 4>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 256:   launch_stft_small<R, 8>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 512:   launch_stft_mid<R, 16, true>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 1024:  launch_stft_mid<R, 32, true>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 2048:  launch_stft_mid<R, 2, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 4096:  launch_stft_mid<R, 4, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        case 8192:  launch_stft_mid<R, 8, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
+        default:    launch_stft_mid<R, 16, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
+    }
+}
+
+}  // namespace
+
+bool dsc_stft_regs_supports(int n_fft) { return n_fft >= 64 && n_fft <= 32768 && (n_fft & (n_fft - 1)) == 0; }
+
+// Fused forward STFT (dsc_stft): x [n_lines / n_frames][T] reals, out [n_lines][n_fft/2 + 1] bins; the plan tables of the
+// n_fft/2-point REAL plan.  x_bytes: see stft_frames.
+void dsc_launch_stft_regs(const void *x, const void *w, void *out, long long n_lines, int n_fft, int T, int n_frames, int hop, int pad,
+                          bool reflect, bool single_precision, int x_bytes, const void *tw_full, const void *tw_real, hipStream_t stream) {
+    if (n_lines <= 0) return;
+    if (single_precision) {
+        const stft_frames<float> fr{(const float *) x, (const float *) w, x_bytes, T, n_frames, hop, pad, reflect ? 1 : 0};
+        launch_stft_len<float>(n_fft / 2, out, n_lines, tw_full, tw_real, fr, stream);
+    } else {
+        const stft_frames<double> fr{(const double *) x, (const double *) w, x_bytes, T, n_frames, hop, pad, reflect ? 1 : 0};
+        launch_stft_len<double>(n_fft / 2, out, n_lines, tw_full, tw_real, fr, stream);
+    }
 }

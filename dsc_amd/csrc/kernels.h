@@ -167,6 +167,25 @@ void dsc_launch_fft_regs_mid(const void *in, void *out, long long n_lines, int L
 void dsc_launch_filter_regs_mid(const void *s, const void *H, void *y, long long n_lines, int L, bool single_precision, const void *tw_full,
                                 const void *tw_real, long long in_pitch, int in_len, hipStream_t stream);
 
+// ---- short-time transforms (dsc_stft / dsc_istft, stft.cpp) -----------------------------------
+// Fused forward route (fft_regs_mid.hip), n_fft = 64 .. 32768: frames of x [rows][T] (rows = n_lines / n_frames) starting at
+// f * hop - pad, reflected (reflect) or zero outside [0, T), times w [n_fft] (NULL = ones), through the packed-real register
+// transform into out [n_lines][n_fft/2 + 1].  Tables of the n_fft/2-point REAL plan; x_bytes >= rows T elem, and
+// (rows + 1) T elem + n_fft elem < 2^31.
+bool dsc_stft_regs_supports(int n_fft);
+void dsc_launch_stft_regs(const void *x, const void *w, void *out, long long n_lines, int n_fft, int T, int n_frames, int hop, int pad,
+                          bool reflect, bool single_precision, int x_bytes, const void *tw_full, const void *tw_real, hipStream_t stream);
+// Frame-and-window gather (fft_stft.hip): frames [n_lines][n_fft] reals <- frames q0 .. q0 + n_lines - 1 (flattened (row, frame)) of x,
+// same mapping as above
+void dsc_launch_stft_frames(const void *x, const void *w, void *frames, long long q0, long long n_lines, int n_fft, long long T, int n_frames,
+                            int hop, int pad, bool reflect, bool single_precision, hipStream_t stream);
+// Overlap-add gather (fft_stft.hip).  frames [rows][fpr][n_fft] reals hold frames fa .. fa + fpr - 1 of `rows` consecutive rows starting
+// at row r0; writes y[r][p - pad] for padded positions p in [p0, p1) with 0 <= p - pad < length: the sum over the frames f in
+// [fa, fa + fpr) ∩ [0, n_frames) covering p (f hop <= p < f hop + n_fft), in increasing f, of frame[p - f hop] w[p - f hop], divided by
+// the sum of w^2 over the same frames (0 where no frame covers p).  y: [.., length] reals; no atomics.
+void dsc_launch_istft_ola(const void *frames, const void *w, void *y, long long r0, long long rows, int fa, int fpr, int n_fft, int hop,
+                          int n_frames, int pad, long long p0, long long p1, int length, bool single_precision, hipStream_t stream);
+
 // ---- element-wise ------------------------------------------------------------------------
 // dtype codes are dsc_dtype values (0 f32, 1 f64, 2 c32, 3 c64)
 void dsc_launch_cast(const void *in, int in_dtype, void *out, int out_dtype, long long ne, hipStream_t stream);

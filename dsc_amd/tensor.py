@@ -5,6 +5,7 @@ arange / randn :615-620, fft/ifft/rfft/irfft :693-726).
 Differences forced by the device arena (see include/dsc_mi355x.h): `numpy()` and
 `from_numpy()` COPY through dsc_copy_to_host / dsc_copy_from_host instead of viewing /
 memmoving the data pointer."""
+import builtins
 from typing import List, Tuple, Union
 
 import numpy as np
@@ -412,3 +413,170 @@ def fftfreq(n: int, d: float = 1.0, dtype: Dtype = Dtype.F32) -> Tensor:   # pyt
 
 def rfftfreq(n: int, d: float = 1.0, dtype: Dtype = Dtype.F32) -> Tensor:  # python/dsc/tensor.py:733-734
     return Tensor(B.dsc_rfftfreq(_get_ctx(), n, d, dtype.value))
+
+
+# ---- short-time transforms (include/dsc_mi355x.h, Section D) -------------------------------------------------------------------
+# torch.stft / torch.istft semantics (onesided, normalized=False, win_length == n_fft) with a FRAMES-MAJOR spectrum
+# [.., n_frames, n_fft // 2 + 1] = torch.stft(...).transpose(-2, -1).  Arguments are checked here and raise ValueError, so that
+# the C library's print-and-exit is never reached from Python.
+
+def _check_stft_args(n_fft: int, hop_length, window, real_dtype: Dtype) -> int:
+    if not isinstance(n_fft, (int, np.integer)) or n_fft < 4 or n_fft > (1 << 20) or n_fft & (n_fft - 1):
+        raise ValueError(f'n_fft must be a power of two in [4, 2^20], got {n_fft}')
+    hop = n_fft // 4 if hop_length is None else int(hop_length)
+    if hop < 1:
+        raise ValueError(f'hop_length must be >= 1, got {hop}')
+    if window is not None:
+        if not isinstance(window, Tensor) or window.n_dim != 1 or len(window) != n_fft:
+            raise ValueError(f'window must be a 1-D Tensor of n_fft = {n_fft} elements')
+        if window.dtype != real_dtype:
+            raise ValueError(f'window dtype {window.dtype} does not match the transform precision {real_dtype}')
+    return hop
+
+
+_INT_MAX = 0x7fffffff                      # a tensor holds at most this many elements (`int ne`)
+
+
+def _check_out(out, shape, dtype: Dtype, what: str):
+    if out is not None and (not isinstance(out, Tensor) or tuple(out.shape) != tuple(shape) or out.dtype != dtype):
+        got = (tuple(out.shape), out.dtype) if isinstance(out, Tensor) else type(out).__name__
+        raise ValueError(f'{what}: out must be a {dtype} Tensor of shape {tuple(shape)}, got {got}')
+
+
+def stft_n_frames(T: int, n_fft: int, hop_length: int, center: bool = True) -> int:
+    """Frames of a length-T signal: 1 + T // hop with center, 1 + (T - n_fft) // hop without."""
+    return 1 + T // hop_length if center else 1 + (T - n_fft) // hop_length
+
+
+def stft(x: Tensor, n_fft: int, hop_length: Union[int, None] = None, window: Union[Tensor, None] = None, center: bool = True,
+         pad_mode: str = 'reflect', out: Union[Tensor, None] = None) -> Tensor:
+    """Short-time Fourier transform of real x [.., T] (at most 3 dims) -> complex [.., n_frames, n_fft // 2 + 1] (frames-major:
+    torch.stft(...).transpose(-2, -1)).  hop_length defaults to n_fft // 4; window None = rectangular; pad_mode 'reflect' or
+    'constant' (zeros), used with center only."""
+    if x.dtype not in (Dtype.F32, Dtype.F64):
+        raise ValueError(f'stft input must be real (f32 / f64), got {x.dtype}')
+    if not 1 <= x.n_dim <= 3:
+        raise ValueError(f'stft input has 1 to 3 dimensions, got {x.n_dim}')
+    hop = _check_stft_args(n_fft, hop_length, window, x.dtype)
+    if pad_mode not in ('reflect', 'constant'):
+        raise ValueError(f"pad_mode must be 'reflect' or 'constant', got {pad_mode!r}")
+    T = x.shape[-1]
+    if center and pad_mode == 'reflect' and T <= n_fft // 2:
+        raise ValueError(f'reflect padding needs T > n_fft // 2 (T = {T}, n_fft = {n_fft})')
+    if not center and T < n_fft:
+        raise ValueError(f'without center the signal needs T >= n_fft (T = {T}, n_fft = {n_fft})')
+    n_frames = stft_n_frames(T, n_fft, hop, center)
+    shape = tuple(x.shape[:-1]) + (n_frames, n_fft // 2 + 1)
+    if int(np.prod(shape, dtype=np.int64)) > _INT_MAX:
+        raise ValueError(f'stft output {shape} has more than 2^31 - 1 elements')
+    _check_out(out, shape, Dtype.C32 if x.dtype == Dtype.F32 else Dtype.C64, 'stft')
+    return Tensor(B.dsc_stft(_get_ctx(), x._c_ptr, n_fft, hop, _c_ptr_or_none(window), bool(center), 0 if pad_mode == 'reflect' else 1,
+                             _c_ptr_or_none(out)), out is not None)
+
+
+def _nola_min(w2: np.ndarray, n_fft: int, hop: int, n_frames: int, start: int, end: int) -> float:
+    """Smallest squared-window envelope over padded output positions [start, end) (end clipped to the last frame's end); inf if
+    the range is empty.  O(n_fft + hop) host work, the same numbers in the same order as nola_min in dsc_amd/csrc/stft.cpp: with
+    W[k, r] = w2[r + k hop] (zero past n_fft), position p = q hop + r sums W[k, r] over k in [max(0, q - n_frames + 1),
+    min(K - 1, q)] — prefix sums down column r (suffix sums where the range reaches the last row) — and positions more than
+    (K + 1) hop from both ends all see the full column sum, so one period of them stands for the rest.
+    (builtins.min: this module defines its own min / max / sum.)"""
+    end = builtins.min(end, n_fft + hop * (n_frames - 1))
+    if end <= start:
+        return float('inf')
+    K = -(-n_fft // hop)
+    W = np.zeros(K * hop)
+    W[:n_fft] = w2
+    W = W.reshape(K, hop)
+    pre = np.concatenate([np.zeros((1, hop)), np.cumsum(W, axis=0)])                 # pre[k] = rows < k
+    suf = np.concatenate([np.cumsum(W[::-1], axis=0)[::-1], np.zeros((1, hop))])      # suf[k] = rows >= k
+
+    def env(p):
+        q, r = p // hop, p % hop
+        lo, hi = np.maximum(0, q - n_frames + 1), np.minimum(K - 1, q)
+        e = np.where(lo == 0, pre[hi + 1, r], np.where(hi == K - 1, suf[lo, r], pre[hi + 1, r] - pre[lo, r]))
+        return np.where(hi < lo, 0.0, e)
+
+    span = (K + 1) * hop
+    h_end = builtins.min(end, start + span)
+    t_start = builtins.max(h_end, end - span)
+    best = float(env(np.arange(start, h_end, dtype=np.int64)).min())
+    if t_start < end:
+        best = builtins.min(best, float(env(np.arange(t_start, end, dtype=np.int64)).min()))
+    if h_end < t_start:
+        best = builtins.min(best, float(suf[0, np.arange(h_end, builtins.min(t_start, h_end + hop)) % hop].min()))
+    return best
+
+
+def istft(X: Tensor, n_fft: int, hop_length: Union[int, None] = None, window: Union[Tensor, None] = None, center: bool = True,
+          length: Union[int, None] = None, out: Union[Tensor, None] = None) -> Tensor:
+    """Inverse of stft: complex X [.., n_frames, n_fft // 2 + 1] -> real [.., length] (torch.istft semantics).  length None = the
+    natural length; samples past the last frame are zero.  Raises ValueError when the window violates NOLA (squared-window
+    envelope < 1e-11 where the output is read); that check copies the window to the host (synchronous)."""
+    if X.dtype not in (Dtype.C32, Dtype.C64):
+        raise ValueError(f'istft input must be complex (c32 / c64), got {X.dtype}')
+    if not 2 <= X.n_dim <= 4:
+        raise ValueError(f'istft input must be [.., n_frames, n_fft // 2 + 1], got {X.n_dim} dimensions')
+    real_dtype = Dtype.F32 if X.dtype == Dtype.C32 else Dtype.F64
+    hop = _check_stft_args(n_fft, hop_length, window, real_dtype)
+    n_frames, bins = X.shape[-2], X.shape[-1]
+    if bins != n_fft // 2 + 1:
+        raise ValueError(f'istft input has {bins} bins, n_fft = {n_fft} needs {n_fft // 2 + 1}')
+    pad = n_fft // 2 if center else 0
+    natural = hop * (n_frames - 1) + (0 if center else n_fft)
+    n_out = natural if length is None or length <= 0 else int(length)
+    if n_out < 1:
+        raise ValueError(f'istft output length {n_out} < 1')
+    shape = tuple(X.shape[:-2]) + (n_out,)
+    if int(np.prod(shape, dtype=np.int64)) > _INT_MAX:
+        raise ValueError(f'istft output {shape} has more than 2^31 - 1 elements')
+    _check_out(out, shape, real_dtype, 'istft')
+    w2 = np.ones(n_fft) if window is None else window.numpy().astype(np.float64) ** 2
+    env_min = _nola_min(w2, n_fft, hop, n_frames, pad, pad + n_out)
+    if not env_min >= 1e-11:
+        raise ValueError(f'window overlap-add envelope {env_min:.3g} < 1e-11: the window / hop violate NOLA')
+    return Tensor(B.dsc_istft(_get_ctx(), X._c_ptr, n_fft, hop, _c_ptr_or_none(window), bool(center), n_out, _c_ptr_or_none(out)),
+                  out is not None)
+
+
+# ---- windows (torch's definitions; computed on the host in f64, then uploaded) ---------------------------------------------------
+def _window(values: np.ndarray, dtype: Dtype) -> Tensor:
+    if dtype not in (Dtype.F32, Dtype.F64):
+        raise ValueError(f'window dtype must be f32 or f64, got {dtype}')
+    return from_numpy(values.astype(DTYPE_TO_NP[dtype]))
+
+
+def _cosine_sum(n: int, periodic: bool, coeffs) -> np.ndarray:
+    if n < 0:
+        raise ValueError(f'window length must be >= 0, got {n}')
+    if n == 1:
+        return np.ones(1)
+    m = n if periodic else n - 1
+    k = np.arange(n, dtype=np.float64)
+    return np.sum([(-1) ** i * a * np.cos(2.0 * np.pi * i * k / m) for i, a in enumerate(coeffs)], axis=0)
+
+
+def hann_window(n: int, periodic: bool = True, dtype: Dtype = Dtype.F32) -> Tensor:
+    """torch.hann_window: 0.5 - 0.5 cos(2 pi k / N), N = n (periodic) or n - 1."""
+    return _window(_cosine_sum(n, periodic, (0.5, 0.5)), dtype)
+
+
+def hamming_window(n: int, periodic: bool = True, dtype: Dtype = Dtype.F32) -> Tensor:
+    """torch.hamming_window: 0.54 - 0.46 cos(2 pi k / N)."""
+    return _window(_cosine_sum(n, periodic, (0.54, 0.46)), dtype)
+
+
+def blackman_window(n: int, periodic: bool = True, dtype: Dtype = Dtype.F32) -> Tensor:
+    """torch.blackman_window: 0.42 - 0.5 cos(2 pi k / N) + 0.08 cos(4 pi k / N)."""
+    return _window(_cosine_sum(n, periodic, (0.42, 0.5, 0.08)), dtype)
+
+
+def kaiser_window(n: int, periodic: bool = True, beta: float = 12.0, dtype: Dtype = Dtype.F32) -> Tensor:
+    """torch.kaiser_window: I0(beta sqrt(1 - (2 k / N - 1)^2)) / I0(beta), N = n (periodic) or n - 1."""
+    if n < 0:
+        raise ValueError(f'window length must be >= 0, got {n}')
+    if n == 1:
+        return _window(np.ones(1), dtype)
+    m = n if periodic else n - 1
+    k = np.arange(n, dtype=np.float64)
+    return _window(np.i0(beta * np.sqrt(np.maximum(0.0, 1.0 - (2.0 * k / m - 1.0) ** 2))) / np.i0(beta), dtype)

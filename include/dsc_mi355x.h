@@ -251,6 +251,29 @@ dsc_tensor *dsc_filter_fft(dsc_ctx *ctx, const dsc_tensor *s, const dsc_tensor *
 const char *dsc_last_fft_path(dsc_ctx *ctx);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section D — short-time transforms (no reference counterpart).
+ *
+ * torch.stft / torch.istft with onesided=True, normalized=False and win_length == n_fft, except for the layout: the
+ * spectrum is FRAMES-MAJOR, [.., n_frames, n_fft/2 + 1] — torch.stft(...).transpose(-2, -1) — each frame's bins contiguous
+ * like a batched dsc_rfft.  n_fft is a power of two, 4 <= n_fft <= 2^20, never rounded; hop >= 1 (larger than n_fft too).
+ * window: real [n_fft] of the transform's precision, or NULL = ones.  Argument errors print and exit like every operator.
+ * dsc_last_fft_path: "stft_regs" (one pass, framing and window in the load of the register kernels: n_fft 64 .. 32768),
+ * "stft_composed" (windowed frames gathered into scratch, then the rfft routes; DSC_NO_STFT_FUSED=1 forces it, and so does a
+ * row too long for the fused kernels' 31-bit buffer offsets: T * element size + n_fft * element size near 2 GB), "istft_ola".
+ */
+/* pad_mode: 0 = reflect (torch default), 1 = constant zeros.  window: real [n_fft] of x's precision, or NULL = ones.
+ * x real [.., T] (f32 -> c32, f64 -> c64, at most 3 dims); out [.., n_frames, n_fft/2+1] or NULL.
+ * n_frames = 1 + T / hop (center), 1 + (T - n_fft) / hop (not center).  center with reflect padding needs T > n_fft/2,
+ * no center T >= n_fft. */
+dsc_tensor *dsc_stft(dsc_ctx *ctx, const dsc_tensor *x, int n_fft, int hop, const dsc_tensor *window,
+                     bool center, int pad_mode, dsc_tensor *out);
+/* X complex [.., n_frames, n_fft/2+1]; length <= 0 = the natural length (hop (n_frames - 1), plus n_fft without center);
+ * out real [.., length] or NULL.  Samples past the last frame are zero.  NOLA: the squared-window envelope must be >= 1e-11
+ * wherever the output is read; the check copies the window (n_fft elements) to the host, which SYNCHRONISES the stream. */
+dsc_tensor *dsc_istft(dsc_ctx *ctx, const dsc_tensor *X, int n_fft, int hop, const dsc_tensor *window,
+                      bool center, int length, dsc_tensor *out);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
