@@ -170,6 +170,8 @@ dsc_filter_fft = _sig('dsc_filter_fft', _DscTensor_p, _DscCtx, _DscTensor_p, _Ds
 dsc_last_fft_path = _sig('dsc_last_fft_path', c_char_p, _DscCtx)
 dsc_stft = _sig('dsc_stft', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p, c_bool, c_int, _DscTensor_p)
 dsc_istft = _sig('dsc_istft', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p, c_bool, c_int, _DscTensor_p)
+dsc_convolve = _sig('dsc_convolve', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, _DscTensor_p)
+dsc_correlate = _sig('dsc_correlate', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, _DscTensor_p)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

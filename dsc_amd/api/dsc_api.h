@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft` and `dsc::stft / istft`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` and `dsc::convolve / correlate`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -241,6 +241,13 @@ template<typename T>
 static inline tensor<T> istft(const tensor<T> &X, int n_fft, int hop, const tensor<T> *window = nullptr, bool center = true, int length = -1) noexcept {
     return dsc_istft(ctx, X.x_, n_fft, hop, window ? window->x_ : nullptr, center, length, nullptr);
 }
+
+// Section E of dsc_mi355x.h: linear convolution of every row of x with one filter h; mode 0 = full, 1 = same, 2 = valid
+// (numpy.convolve / numpy.correlate along the last axis).
+template<typename T>
+static inline tensor<T> convolve(const tensor<T> &x, const tensor<T> &h, int mode = 0) noexcept { return dsc_convolve(ctx, x.x_, h.x_, mode, nullptr); }
+template<typename T>
+static inline tensor<T> correlate(const tensor<T> &x, const tensor<T> &h, int mode = 2) noexcept { return dsc_correlate(ctx, x.x_, h.x_, mode, nullptr); }
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

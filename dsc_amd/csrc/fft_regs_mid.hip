@@ -274,6 +274,22 @@ __device__ __forceinline__ cpx<R> frame_pair_gather(const stft_frames<R> &fr, __
     return cpx<R>{buf_load_real<POL>(rx, frame_sample_off(fr, row_off, s), 0, R{}).x,
                   buf_load_real<POL>(rx, frame_sample_off(fr, row_off, s + 1), 0, R{}).x};
 }
+// v[j1] = samples s0 + 2 (T j1 + t), + 1 of the row at element row_off: the packed-real input of one frame line, 2L samples.  Frames
+// inside [0, T) that start on an even element load 8-/16-byte pairs; the others go sample by sample (frame_pair_gather).
+template<int POL, int T, int L, typename R>
+__device__ __forceinline__ void load_frame_line(cpx<R> (&v)[32], const stft_frames<R> &fr, __amdgpu_buffer_rsrc_t rx, int row_off, int s0,
+                                                int t) {
+    constexpr int CB = 2 * (int) sizeof(R);
+    const bool direct = ((row_off + s0) & 1) == 0 && s0 >= 0 && s0 + 2 * L <= fr.T;
+    if (direct) {
+        const int vfr = (row_off + s0) * (int) sizeof(R) + t * CB;
+#pragma unroll
+        for (int j1 = 0; j1 < 32; ++j1) v[j1] = buf_load<POL>(rx, vfr, T * j1 * CB, R{});
+    } else {
+#pragma unroll
+        for (int j1 = 0; j1 < 32; ++j1) v[j1] = frame_pair_gather<POL>(fr, rx, row_off, s0 + 2 * (T * j1 + t));
+    }
+}
 template<typename R>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t window_rsrc(const stft_frames<R> &fr, int n) {
     return __builtin_amdgcn_make_buffer_rsrc((void *) fr.w, 0, fr.w ? n * (int) sizeof(R) : 0, 0x00020000);
@@ -359,15 +375,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
         const long long line = line0 + g;
         const int row = (int) (line / fr.n_frames);
         const int row_off = row * fr.T, s0 = (int) (line - (long long) row * fr.n_frames) * fr.hop - fr.pad;
-        const bool direct = ((row_off + s0) & 1) == 0 && s0 >= 0 && s0 + 2 * L <= fr.T;
-        if (direct) {
-            const int vfr = (row_off + s0) * (int) sizeof(R) + t * CB;
-#pragma unroll
-            for (int j1 = 0; j1 < 32; ++j1) v[j1] = buf_load<LOADP>(rin, vfr, T * j1 * CB, R{});
-        } else {
-#pragma unroll
-            for (int j1 = 0; j1 < 32; ++j1) v[j1] = frame_pair_gather<LOADP>(fr, rin, row_off, s0 + 2 * (T * j1 + t));
-        }
+        load_frame_line<LOADP, T, L>(v, fr, rin, row_off, s0, t);
         if (fr.w != nullptr) {
             const __amdgpu_buffer_rsrc_t rw = window_rsrc(fr, 2 * L);
 #pragma unroll
@@ -614,15 +622,38 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
     } while (PIPE);
 }
 
+// Overlap-save blocks (dsc_convolve, the fused route).  Line q = (row, block b) of the filter kernel is the frame src (w = NULL, reflect = 0,
+// n_frames = blocks per row, pad = D - n0): samples x[row][n0 + b hop - D + i], i < 2L, zero outside [0, T).  Of the circular
+// convolution only samples [D, 2L) are linear (D >= M - 1, even); sample j goes to y[row][b hop + j - D] if that is < T_out.
+template<typename R> struct conv_frames {
+    stft_frames<R> src;
+    R *y;                // [rows][T_out]
+    int y_bytes;         // descriptor range of y: rows T_out sizeof(R) < 2^31 (host)
+    int D, T_out;
+};
+
+template<int POL>
+__device__ __forceinline__ void buf_store_real(float a, __amdgpu_buffer_rsrc_t r, int voff) {
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a), r, voff, 0, POL);
+}
+template<int POL>
+__device__ __forceinline__ void buf_store_real(double a, __amdgpu_buffer_rsrc_t r, int voff) {
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, a), r, voff, 0, POL);
+}
+
 // ------------------------------------------------------------------------------------------------
 // Fused README filterFFT (README.md:113-135) at the mid sizes: y = irfft(rfft(s, 2L) * H), H [L + 1] bins shared by all
 // rows.  Forward passes, packed-real pass on the pair (k, L-k), times (H[k], H[L-k]), inverse pre-pass on the same pair
 // in the same thread, one staging round trip to bring the pairs back to the load layout, inverse passes: the spectrum
 // never leaves the CU.  s rows may be shorter than 2L (zero padded) or longer (cropped).
-template<typename R, int B, bool TWO>
+// SRC: empty (the rows of s), or conv_frames<R> (s, y, in_pitch_b and in_len_b unused): overlap-save blocks in, the linear part of each
+// out.  An empty pack leaves the kernel's signature and code as they are without frames.
+template<typename R, int B, bool TWO, typename... SRC>
 __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>::WAVES_PER_EU)) void fft_mid_filter_kernel(
     const R *__restrict__ s, const cpx<R> *__restrict__ H, cpx<R> *__restrict__ y, long long n_lines, const cpx<R> *__restrict__ tw_full,
-    const cpx<R> *__restrict__ tw_real, int in_pitch_b, int in_len_b) {
+    const cpx<R> *__restrict__ tw_real, int in_pitch_b, int in_len_b, SRC... frames) {
+    constexpr bool FRAMES = sizeof...(SRC) != 0;
+    const auto fr = frames_of(frames...);
     using C = cpx<R>;
     using cfg = mid_cfg<R, B, TWO, 1>;
     constexpr int T = cfg::T, L = cfg::L, G = cfg::G, NT = cfg::NT, SP = cfg::SP, CPT = cfg::CPT, COLS = cfg::COLS;
@@ -636,20 +667,33 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
     const long long line0 = (long long) blockIdx.x * G;
     const long long left = n_lines - line0;
     const int n_valid = left < G ? (int) left : G;
-    const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) s + line0 * in_pitch_b), 0,
-                                                                         (n_valid - 1) * in_pitch_b + in_len_b, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *) (y + line0 * L), 0, n_valid * L * CB, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rin = [&] {
+        if constexpr (FRAMES) return __builtin_amdgcn_make_buffer_rsrc((void *) fr.src.x, 0, fr.src.x_bytes, 0x00020000);
+        else return __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) s + line0 * in_pitch_b), 0, (n_valid - 1) * in_pitch_b + in_len_b,
+                                                      0x00020000);
+    }();
+    const __amdgpu_buffer_rsrc_t rout = [&] {
+        if constexpr (FRAMES) return __builtin_amdgcn_make_buffer_rsrc((void *) fr.y, 0, fr.y_bytes, 0x00020000);
+        else return __builtin_amdgcn_make_buffer_rsrc((void *) (y + line0 * L), 0, n_valid * L * CB, 0x00020000);
+    }();
     const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void *) H, 0, (L + 1) * CB, 0x00020000);
     const int vin = g * in_pitch_b + t * CB, vout = (g * L + t) * CB;
     R *stage = plane + g * SP;
     for (int i = tid; i < cfg::TABLE; i += NT) wtab[i] = tw_full[(long long) i * cfg::TABLE_STRIDE];
 
     C v[32];
+    if constexpr (FRAMES) {                                               // v[j1] = samples 2 (T j1 + t), + 1 of block line0 + g
+        const long long line = line0 + g;
+        const int row = (int) (line / fr.src.n_frames);
+        const int row_off = row * fr.src.T, s0 = (int) (line - (long long) row * fr.src.n_frames) * fr.src.hop - fr.src.pad;
+        load_frame_line<kCached, T, L>(v, fr.src, rin, row_off, s0, t);
+    } else {
 #pragma unroll
-    for (int j1 = 0; j1 < 32; ++j1) {                                     // sample pairs past the valid length read zero
-        const int eoff = (T * j1 + t) * CB;
-        v[j1] = buf_load<kCached>(rin, eoff < in_len_b ? vin : 0x7f000000, T * j1 * CB, R{});
-        if (eoff + CB > in_len_b) v[j1].y = (R) 0;
+        for (int j1 = 0; j1 < 32; ++j1) {                                 // sample pairs past the valid length read zero
+            const int eoff = (T * j1 + t) * CB;
+            v[j1] = buf_load<kCached>(rin, eoff < in_len_b ? vin : 0x7f000000, T * j1 * CB, R{});
+            if (eoff + CB > in_len_b) v[j1].y = (R) 0;
+        }
     }
     __syncthreads();
     mid_passes<R, B, TWO, false, 1>(v, plane, wtab, tw_full, g, t, tid);  // v[i B + p] = Z[(t + T i) + COLS brev(p)]
@@ -794,13 +838,45 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
     asm volatile("" : "+v"(wtab_inv));
     mid_passes<R, B, TWO, true, 1>(v, plane, wtab_inv, tw_full, g, t, tid);
     const R scale = (R) (1.0 / (double) L);                               // 2/(2n), dsc_fft.h:232
+    if constexpr (FRAMES) {
+        // v[i B + p] = samples 2k, 2k + 1, k = (t + T i) + COLS brev(p).  Kept: 2k >= D (D even: both samples), stored at out index
+        // o = b hop + 2k - D < T_out — the last block of a row reaches past T_out, and with several rows per group those samples
+        // would land on the next row.  A pair whose element offset is odd (odd T_out, rows after the first) goes as two scalars.
+        // (o and the element offset of the thread's first pair go through an opaque copy, so that the per-pair offsets are not
+        // computed before the inverse passes and held through them: f64 N = 512 228 -> 184 VGPRs)
+        const long long line = line0 + g;
+        const int row = (int) (line / fr.src.n_frames);
+        const int b = (int) (line - (long long) row * fr.src.n_frames);
+        int ob = b * fr.src.hop - fr.D + 2 * t, eb = row * fr.T_out + ob;
+        asm volatile("" : "+v"(ob), "+v"(eb));
+        const int o_lo = b * fr.src.hop, o_hi = line < n_lines ? fr.T_out : 0;       // kept: o in [b hop, T_out) of a live line
+        constexpr int RB = (int) sizeof(R);
 #pragma unroll
-    for (int i = 0; i < CPT; ++i)
+        for (int i = 0; i < CPT; ++i)
 #pragma unroll
-        for (int p = 0; p < B; ++p) {
-            const C r = v[i * B + p];
-            buf_store<kStream>(C{r.x * scale, r.y * scale}, rout, vout, (T * i + COLS * brev(p, LOGB)) * CB);
-        }
+            for (int p = 0; p < B; ++p) {
+                const int c = 2 * (T * i + COLS * brev(p, LOGB));
+                const int o = ob + c;
+                if (o >= o_lo && o < o_hi) {
+                    const C r = C{v[i * B + p].x * scale, v[i * B + p].y * scale};
+                    const int e = eb + c;
+                    if ((e & 1) == 0 && o + 1 < fr.T_out) {
+                        buf_store<kStream>(r, rout, e * RB, 0);
+                    } else {
+                        buf_store_real<kStream>(r.x, rout, e * RB);
+                        if (o + 1 < fr.T_out) buf_store_real<kStream>(r.y, rout, (e + 1) * RB);
+                    }
+                }
+            }
+    } else {
+#pragma unroll
+        for (int i = 0; i < CPT; ++i)
+#pragma unroll
+            for (int p = 0; p < B; ++p) {
+                const C r = v[i * B + p];
+                buf_store<kStream>(C{r.x * scale, r.y * scale}, rout, vout, (T * i + COLS * brev(p, LOGB)) * CB);
+            }
+    }
 }
 
 template<typename R, int B, bool TWO>
@@ -1207,5 +1283,50 @@ void dsc_launch_stft_regs(const void *x, const void *w, void *out, long long n_l
     } else {
         const stft_frames<double> fr{(const double *) x, (const double *) w, x_bytes, T, n_frames, hop, pad, reflect ? 1 : 0};
         launch_stft_len<double>(n_fft / 2, out, n_lines, tw_full, tw_real, fr, stream);
+    }
+}
+
+namespace {
+
+template<typename R, int B, bool TWO>
+void launch_conv(const void *H, long long n_lines, const void *tw_full, const void *tw_real, const conv_frames<R> &fr, hipStream_t stream) {
+    using cfg = mid_cfg<R, B, TWO, 1>;
+    constexpr size_t lds = mid_lds_bytes<R, B, TWO, 1>();
+    static unsigned long long attr_devices = 0;
+    if (dsc_first_use_on_device(attr_devices)) {
+        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_filter_kernel<R, B, TWO, conv_frames<R>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    }
+    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
+    DSC_LAUNCH((fft_mid_filter_kernel<R, B, TWO, conv_frames<R>>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, nullptr,
+               (const cpx<R> *) H, nullptr, n_lines, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, 0, 0, fr);
+}
+
+template<typename R>
+void launch_conv_len(int L, const void *H, long long n_lines, const void *tw_full, const void *tw_real, const conv_frames<R> &fr, hipStream_t stream) {
+    switch (L) {
+        case 256:   launch_conv<R, 8, true>(H, n_lines, tw_full, tw_real, fr, stream); break;
+        case 512:   launch_conv<R, 16, true>(H, n_lines, tw_full, tw_real, fr, stream); break;
+        case 1024:  launch_conv<R, 32, true>(H, n_lines, tw_full, tw_real, fr, stream); break;
+        case 2048:  launch_conv<R, 2, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
+        case 4096:  launch_conv<R, 4, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
+        case 8192:  launch_conv<R, 8, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
+        default:    launch_conv<R, 16, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
+    }
+}
+
+}  // namespace
+
+bool dsc_conv_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n - 1)) == 0; }
+
+// Fused overlap-save (dsc_convolve): see conv_frames and kernels.h.
+void dsc_launch_conv_regs(const void *x, const void *H, void *y, long long n_lines, int n, int T, int n_blocks, int hop, int pad, int D, int T_out,
+                          bool single_precision, int x_bytes, int y_bytes, const void *tw_full, const void *tw_real, hipStream_t stream) {
+    if (n_lines <= 0) return;
+    if (single_precision) {
+        const conv_frames<float> fr{{(const float *) x, nullptr, x_bytes, T, n_blocks, hop, pad, 0}, (float *) y, y_bytes, D, T_out};
+        launch_conv_len<float>(n / 2, H, n_lines, tw_full, tw_real, fr, stream);
+    } else {
+        const conv_frames<double> fr{{(const double *) x, nullptr, x_bytes, T, n_blocks, hop, pad, 0}, (double *) y, y_bytes, D, T_out};
+        launch_conv_len<double>(n / 2, H, n_lines, tw_full, tw_real, fr, stream);
     }
 }

@@ -186,6 +186,21 @@ void dsc_launch_stft_frames(const void *x, const void *w, void *frames, long lon
 void dsc_launch_istft_ola(const void *frames, const void *w, void *y, long long r0, long long rows, int fa, int fpr, int n_fft, int hop,
                           int n_frames, int pad, long long p0, long long p1, int length, bool single_precision, hipStream_t stream);
 
+// ---- linear convolution (dsc_convolve / dsc_correlate, conv.cpp) -------------------------------
+// Fused overlap-save route (fft_regs_mid.hip), n = 512 .. 32768: line q = (row, block b), rows = n_lines / n_blocks, is the frame of
+// x [rows][T] starting at b hop - pad (zero outside [0, T)) through irfft(rfft(frame, n) * H), H [n/2 + 1] bins; its samples
+// [D, n) go to y[row][b hop + j - D] where that is < T_out.  D even, hop = n - D.  Tables of the n/2-point REAL plan;
+// x_bytes = rows T elem with (rows + 1) T elem + n elem < 2^31, y_bytes = rows T_out elem < 2^31.
+bool dsc_conv_regs_supports(int n);
+void dsc_launch_conv_regs(const void *x, const void *H, void *y, long long n_lines, int n, int T, int n_blocks, int hop, int pad, int D, int T_out,
+                          bool single_precision, int x_bytes, int y_bytes, const void *tw_full, const void *tw_real, hipStream_t stream);
+// Composed route's crop-scatter (fft_conv.hip): frames [n_lines][n] reals are the filtered blocks q0 .. q0 + n_lines - 1 (flattened
+// (row, b)); the same mapping to y [..][T_out] as above, hop = n - D
+void dsc_launch_conv_crop(const void *frames, void *y, long long q0, long long n_lines, int n, int D, int n_blocks, long long T_out,
+                          bool single_precision, hipStream_t stream);
+// out[i] = in[n - 1 - i] (fft_conv.hip)
+void dsc_launch_reverse(const void *in, void *out, int n, bool single_precision, hipStream_t stream);
+
 // ---- element-wise ------------------------------------------------------------------------
 // dtype codes are dsc_dtype values (0 f32, 1 f64, 2 c32, 3 c64)
 void dsc_launch_cast(const void *in, int in_dtype, void *out, int out_dtype, long long ne, hipStream_t stream);

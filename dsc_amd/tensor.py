@@ -539,6 +539,52 @@ def istft(X: Tensor, n_fft: int, hop_length: Union[int, None] = None, window: Un
                   out is not None)
 
 
+# ---- linear convolution (include/dsc_mi355x.h, Section E) ------------------------------------------------------------------------
+# Row r of the result = np.convolve(x[r], h, 'full')[n0 : n0 + T_out], n0 = 0 / (M - 1) // 2 / M - 1 for full / same / valid: numpy's
+# convolve / correlate along the last axis whenever M <= T, scipy.signal.fftconvolve(x, h[None], mode, axes=-1) always.
+_CONV_MODES = {'full': 0, 'same': 1, 'valid': 2}
+
+
+def _conv(fn, what: str, x: Tensor, h: Tensor, mode: str, out) -> Tensor:
+    if not isinstance(x, Tensor) or not isinstance(h, Tensor):
+        raise ValueError(f'{what}: x and h must be Tensors')
+    if x.dtype not in (Dtype.F32, Dtype.F64) or h.dtype not in (Dtype.F32, Dtype.F64):
+        raise ValueError(f'{what}: inputs must be real (f32 / f64), got {x.dtype} and {h.dtype}')
+    if h.dtype != x.dtype:
+        raise ValueError(f'{what}: x and h must have the same dtype, got {x.dtype} and {h.dtype}')
+    if not 1 <= x.n_dim <= 3:
+        raise ValueError(f'{what}: x has 1 to 3 dimensions, got {x.n_dim}')
+    if h.n_dim != 1 or h.ne < 1:
+        raise ValueError(f'{what}: h must be 1-D with at least one tap, got shape {h.shape}')
+    if mode not in _CONV_MODES:
+        raise ValueError(f"{what}: mode must be 'full', 'same' or 'valid', got {mode!r}")
+    T, M = x.shape[-1], h.ne
+    if mode == 'valid' and M > T:
+        raise ValueError(f'{what}: valid mode needs len(h) <= T (M = {M}, T = {T})')
+    T_out = {'full': T + M - 1, 'same': T, 'valid': T - M + 1}[mode]
+    shape = tuple(x.shape[:-1]) + (T_out,)
+    if int(np.prod(shape, dtype=np.int64)) > _INT_MAX:
+        raise ValueError(f'{what}: output {shape} has more than 2^31 - 1 elements')
+    _check_out(out, shape, x.dtype, what)
+    if out is not None:
+        es = np.dtype(DTYPE_TO_NP[x.dtype]).itemsize
+        xa, oa = x._c_ptr.contents.data, out._c_ptr.contents.data
+        if oa < xa + x.ne * es and xa < oa + out.ne * es:
+            raise ValueError(f'{what}: out must not share memory with x')
+    return Tensor(fn(_get_ctx(), x._c_ptr, h._c_ptr, _CONV_MODES[mode], _c_ptr_or_none(out)), out is not None)
+
+
+def convolve(x: Tensor, h: Tensor, mode: str = 'full', out: Union[Tensor, None] = None) -> Tensor:
+    """Linear convolution of every row of real x [.., T] (at most 3 dims) with real h [M] of the same dtype: mode 'full'
+    (T + M - 1 samples), 'same' (T) or 'valid' (T - M + 1, needs M <= T).  numpy.convolve along the last axis."""
+    return _conv(B.dsc_convolve, 'convolve', x, h, mode, out)
+
+
+def correlate(x: Tensor, h: Tensor, mode: str = 'valid', out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.correlate along the last axis for real inputs: convolve with h reversed."""
+    return _conv(B.dsc_correlate, 'correlate', x, h, mode, out)
+
+
 # ---- windows (torch's definitions; computed on the host in f64, then uploaded) ---------------------------------------------------
 def _window(values: np.ndarray, dtype: Dtype) -> Tensor:
     if dtype not in (Dtype.F32, Dtype.F64):

@@ -274,6 +274,23 @@ dsc_tensor *dsc_istft(dsc_ctx *ctx, const dsc_tensor *X, int n_fft, int hop, con
                       bool center, int length, dsc_tensor *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section E — linear convolution (no reference counterpart).
+ *
+ * Row r of out = np.convolve(x[r], h, 'full')[n0 : n0 + T_out]: scipy.signal.fftconvolve(x, h[None], mode, axes=-1), which is
+ * np.convolve(x[r], h, mode) whenever M <= T.  Overlap-save in blocks of a power-of-two n points, D = M - 1 rounded up to even
+ * of each block discarded.  Argument errors print and exit like every operator.
+ * dsc_last_fft_path: "conv_regs" (one pass: blocks loaded from x, filtered and cropped in the fused filter kernel; D <= 16384),
+ * "conv_composed" (blocks gathered into scratch, dsc_filter_fft, a crop-scatter kernel; D > 16384, rows too long for 31-bit
+ * buffer offsets, or DSC_NO_CONV_FUSED=1).
+ */
+/* x real [.., T] (f32 or f64, at most 3 dims), h real [M] of the same dtype, broadcast over the rows of x.
+ * mode 0 = full (T + M - 1 samples), 1 = same (T samples, start (M - 1) / 2), 2 = valid (T - M + 1 samples, needs M <= T).
+ * out real [.., T_out] or NULL; it must not share memory with x.  dsc_last_fft_path: "conv_regs" | "conv_composed". */
+dsc_tensor *dsc_convolve(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h, int mode, dsc_tensor *out);
+/* numpy.correlate for real inputs: dsc_convolve with h reversed. */
+dsc_tensor *dsc_correlate(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h, int mode, dsc_tensor *out);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
