@@ -239,11 +239,16 @@ float dsc_timer_stop(dsc_ctx *ctx);
 
 /* Fused README filterFFT (README.md:113-135): out = irfft(rfft(s, n) * H) along the last
  * axis, one launch per batch of rows, the spectrum never written to HBM.
- *   s   real [.., ls]   (f32), zero-padded / cropped to n = 2*(H_bins-1) like dsc_rfft
- *   H   complex [H_bins] (c32) filter spectrum, H_bins = n/2 + 1, broadcast over rows
+ *   s   real [.., ls]   (f32 or f64), zero-padded / cropped to n = 2*(H_bins-1) like dsc_rfft
+ *   H   complex [H_bins] (c32 or c64) filter spectrum, H_bins = n/2 + 1, broadcast over rows;
+ *       the imaginary parts of bins 0 and n/2 are ignored, as irfft ignores them
  *   out real [.., n] or NULL
- * Equals dsc_irfft(dsc_mul(dsc_rfft(s, n), H)) within float rounding.  Falls back to
- * exactly that three-op composition for sizes without a fused kernel. */
+ * Equals dsc_irfft(dsc_mul(dsc_rfft(s, n), H)) within float rounding.  Fused for f32 + c32
+ * at n = 512 .. 65536 and f64 + c64 at n = 512 .. 32768 ("filter_mid_regs",
+ * "filter_64k_regs").  Everything else runs exactly that three-op composition
+ * ("filter_composed"): n <= 256, f64 at n = 65536, n >= 131072, rows with ls * 512 >= 2^30
+ * at n <= 32768, and mixed precisions (f32 + c64, f64 + c32), whose output dsc_mul
+ * promotes to f64. */
 dsc_tensor *dsc_filter_fft(dsc_ctx *ctx, const dsc_tensor *s, const dsc_tensor *H, dsc_tensor *out);
 
 /* Name of the kernel path the last FFT-family call took ("r2c_64k_regs", "generic_lds",

@@ -883,8 +883,11 @@ def test_column_kernel_every_length_and_mode(dsc, dt, L):
 @pytest.mark.parametrize('n', [512, 2048, 8192, 32768])
 def test_fused_filter_mid_sizes(dsc, dt, n):
     """dsc_filter_fft (README.md:113-135 as one call) on the fused mid-size kernel: y = irfft(rfft(s, n) * H) against the
-    oracle's three-operator composition, full rows, zero-padded rows (the README pads s inside rfft) and ragged row counts."""
+    oracle's three-operator composition and the long-double reference, every row of full rows, zero-padded rows (the README pads s
+    inside rfft) and ragged row counts."""
     from oracle import port
+    from tests.test_filter_ref import TAU, filter_err, ref_filter
+    tau = TAU[np.dtype(dt)]
     rng = np.random.default_rng(n)
     taps = np.zeros(n, dt)
     taps[:61] = rng.standard_normal(61)
@@ -896,14 +899,18 @@ def test_fused_filter_mid_sizes(dsc, dt, n):
         assert dsc.last_fft_path() == 'filter_mid_regs', (n, ls)
         assert y.shape == (rows, n)
         yh = y.numpy()
-        for r in (0, rows - 1):
+        for r in range(rows):
             want = port.irfft(port.mul(port.rfft(s[r], n), H))
             assert_close(yh[r], want, what=f'filter n={n} ls={ls} row {r}')
-    # linear convolution check (the README's use): y[:ls + lb - 1] == convolve(s, b)
+        e = filter_err(yh, ref_filter(s, H, n), s, H, n, tau)
+        assert e <= 1, f'filter n={n} ls={ls}: err / bound {e:.3g}'
+    # linear convolution check (the README's use): y[:ls + lb - 1] == convolve(s, b), here all n samples, in long double
     s = rng.standard_normal((2, n - 61 + 1)).astype(dt)
     y = dsc.filter_fft(dsc.from_numpy(s), tH)[:, :n].numpy()
-    want = np.stack([np.convolve(r.astype(np.float64), taps[:61].astype(np.float64)) for r in s])
-    assert np.abs(y - want).max() <= (2e-3 if dt == np.float32 else 1e-10)
+    want = np.stack([np.convolve(r.astype(np.longdouble), taps[:61].astype(np.longdouble)) for r in s])
+    assert want.shape == (2, n)
+    e = filter_err(y, want, s, H, n, tau)
+    assert e <= 1, f'linear convolution n={n}: err / bound {e:.3g}'
 
 
 @pytest.mark.parametrize('dt', [np.float32, np.float64])
