@@ -63,6 +63,28 @@ static dsc_fft_plan *find_plan(dsc_ctx *ctx, int n, dsc_fft_type fft_type, dsc_d
     return plan;
 }
 
+// Bytes of the one main-arena block a plan's tables take: the n-th roots, the 2n-th roots of a REAL plan, the register kernels' tables.
+static size_t plan_bytes(int fft_n, dsc_fft_type fft_type, dsc_dtype twd, size_t *full, size_t *real, size_t *aux) {
+    const size_t real_sz = twd == DSC_F32 ? 4 : 8;
+    const bool regs64k = twd == DSC_F32 && fft_n == 32768;          // the 65536-point real and the 32768-point complex register kernels
+    *full = DSC_ALIGN_UP((size_t) fft_n * 2 * real_sz, DSC_DEVICE_ALIGN);
+    *real = fft_type == DSC_FFT_REAL ? DSC_ALIGN_UP(((size_t) fft_n + 1) * 2 * real_sz, DSC_DEVICE_ALIGN) : 0;
+    *aux = regs64k ? DSC_ALIGN_UP(dsc_r2c64k_table_bytes(), DSC_DEVICE_ALIGN) : 0;
+    return *full + *real + *aux;
+}
+
+// Main-arena bytes dsc_plan_fft(ctx, n, COMPLEX, dtype) would allocate now: 0 when the plan is cached.  Leaves the LRU counts alone.
+static size_t missing_complex_plan_bytes(const dsc_ctx *ctx, int n, dsc_dtype dtype) {
+    const int fft_n = dsc_pow2_n(n);
+    const dsc_dtype twd = dsc_is_single(dtype) ? DSC_F32 : DSC_F64;
+    for (int i = 0; i < DSC_MAX_FFT_PLANS; ++i) {
+        const dsc_fft_plan *p = ctx->fft_plans[i];
+        if (p != nullptr && p->n == fft_n && p->fft_type == DSC_FFT_COMPLEX && p->dtype == twd) return 0;
+    }
+    size_t full, real, aux;
+    return plan_bytes(fft_n, DSC_FFT_COMPLEX, twd, &full, &real, &aux);
+}
+
 // dsc.cpp:218-267.  The reference's table is the concatenation of every radix-2 stage's
 // twiddles in the transform precision (dsc_fft.h:33-55); ours is one table of the n-th
 // roots (every stage indexes it with a stride) plus, for REAL plans, the 2n-th roots of the
@@ -90,12 +112,9 @@ extern "C" dsc_fft_plan *dsc_plan_fft(dsc_ctx *ctx, int n, dsc_fft_type fft_type
         ctx->fft_plans[slot] = nullptr;
     }
 
-    const size_t real_sz = twd == DSC_F32 ? 4 : 8;
-    const bool regs64k = twd == DSC_F32 && fft_n == 32768;          // the 65536-point real and the 32768-point complex register kernels
-    const size_t full_bytes = DSC_ALIGN_UP((size_t) fft_n * 2 * real_sz, DSC_DEVICE_ALIGN);
-    const size_t real_bytes = fft_type == DSC_FFT_REAL ? DSC_ALIGN_UP(((size_t) fft_n + 1) * 2 * real_sz, DSC_DEVICE_ALIGN) : 0;
-    const size_t aux_bytes = regs64k ? DSC_ALIGN_UP(dsc_r2c64k_table_bytes(), DSC_DEVICE_ALIGN) : 0;
-    const size_t total = full_bytes + real_bytes + aux_bytes;
+    size_t full_bytes, real_bytes, aux_bytes;
+    const size_t total = plan_bytes(fft_n, fft_type, twd, &full_bytes, &real_bytes, &aux_bytes);
+    const bool regs64k = aux_bytes != 0;
 
     std::vector<char> host(total, 0);
     if (twd == DSC_F32) {
@@ -261,8 +280,13 @@ static void run_job(dsc_ctx *ctx, const fft_job &j) {
             const size_t csz = dsc_dtype_size(j.out->dtype);
             const size_t slice_bytes = (size_t) j.L * inner * csz;                     // pass 1 addresses a whole [n][inner] slice with 32-bit offsets
             const size_t work_bytes = (size_t) j.out->ne * csz;
-            if (slice_bytes < 0x7f000000u && (long long) n1 * inner < (1LL << 30) && (n_lines / inner) * n2 < (1LL << 31) && ctx->main.fits(work_bytes, 0)) {
-                const dsc_dtype cdt = j.out->dtype;
+            // the plan tables not cached yet are allocated with the fatal alloc below: probe for them with `work` (as one block: conservative),
+            // so that a tight context falls through to the routes below instead of exiting
+            const dsc_dtype cdt = j.out->dtype;
+            const size_t plans_bytes = (n1 == n2 ? 0 : missing_complex_plan_bytes(ctx, n1, cdt)) + missing_complex_plan_bytes(ctx, n2, cdt) +
+                                       missing_complex_plan_bytes(ctx, j.L, cdt);
+            if (slice_bytes < 0x7f000000u && (long long) n1 * inner < (1LL << 30) && (n_lines / inner) * n2 < (1LL << 31) &&
+                ctx->main.fits(work_bytes, plans_bytes)) {
                 const dsc_fft_plan *p1 = dsc_plan_fft(ctx, n1, DSC_FFT_COMPLEX, cdt);
                 const dsc_fft_plan *p2 = dsc_plan_fft(ctx, n2, DSC_FFT_COMPLEX, cdt);
                 const dsc_fft_plan *pn = dsc_plan_fft(ctx, j.L, DSC_FFT_COMPLEX, cdt);
@@ -293,8 +317,12 @@ static void run_job(dsc_ctx *ctx, const fft_job &j) {
             const long long slices = n_lines / inner, cc_n = inner / 2;
             const size_t real_slice = (size_t) n * inner * (csz / 2), bins_slice = (size_t) (j.L + 1) * inner * csz;
             const size_t work_bytes = (size_t) slices * n * cc_n * csz;
+            // as above: the uncached tables with `work`.  pn is the 2n-point COMPLEX plan, not the REAL plan run_job made: for f64 at
+            // n = 2^22 a 64 MB table that the routes below never need
+            const size_t plans_bytes = (n1 == n2 ? 0 : missing_complex_plan_bytes(ctx, n1, cdt)) + missing_complex_plan_bytes(ctx, n2, cdt) +
+                                       missing_complex_plan_bytes(ctx, (int) n, cdt);
             if (real_slice < 0x7f000000u && bins_slice < 0x7f000000u && slices * n < (1LL << 31) && slices * n2 < (1LL << 31) &&
-                (long long) n1 * cc_n < (1LL << 30) && ctx->main.fits(work_bytes, 0)) {
+                (long long) n1 * cc_n < (1LL << 30) && ctx->main.fits(work_bytes, plans_bytes)) {
                 const dsc_fft_plan *p1 = dsc_plan_fft(ctx, n1, DSC_FFT_COMPLEX, cdt);
                 const dsc_fft_plan *p2 = dsc_plan_fft(ctx, n2, DSC_FFT_COMPLEX, cdt);
                 const dsc_fft_plan *pn = dsc_plan_fft(ctx, (int) n, DSC_FFT_COMPLEX, cdt);
