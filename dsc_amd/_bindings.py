@@ -172,6 +172,10 @@ dsc_stft = _sig('dsc_stft', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _
 dsc_istft = _sig('dsc_istft', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p, c_bool, c_int, _DscTensor_p)
 dsc_convolve = _sig('dsc_convolve', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, _DscTensor_p)
 dsc_correlate = _sig('dsc_correlate', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, _DscTensor_p)
+dsc_fft2 = _sig('dsc_fft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
+dsc_ifft2 = _sig('dsc_ifft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
+dsc_rfft2 = _sig('dsc_rfft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
+dsc_irfft2 = _sig('dsc_irfft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` and `dsc::convolve / correlate`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate` and `dsc::fft2 / ifft2 / rfft2 / irfft2`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -226,6 +226,16 @@ template<typename T, typename... Args>
 static inline tensor<T> concat(int axis, const tensor<T> &first, const Args &...rest) noexcept {
     return dsc_concat(ctx, axis, 1 + (int) sizeof...(Args), first.x_, rest.x_...);
 }
+
+// Section F of dsc_mi355x.h: 2-D transforms over the last two axes (numpy.fft.fft2 / ifft2 / rfft2 / irfft2, s = (n0, n1))
+template<typename T>
+static inline tensor<T> fft2(const tensor<T> &x, int n0 = -1, int n1 = -1) noexcept { return dsc_fft2(ctx, x.x_, nullptr, n0, n1); }
+template<typename T>
+static inline tensor<T> ifft2(const tensor<T> &x, int n0 = -1, int n1 = -1) noexcept { return dsc_ifft2(ctx, x.x_, nullptr, n0, n1); }
+template<typename T>
+static inline tensor<T> rfft2(const tensor<T> &x, int n0 = -1, int n1 = -1) noexcept { return dsc_rfft2(ctx, x.x_, nullptr, n0, n1); }
+template<typename T>
+static inline tensor<T> irfft2(const tensor<T> &x, int n0 = -1, int n1 = -1) noexcept { return dsc_irfft2(ctx, x.x_, nullptr, n0, n1); }
 
 // README.md:141-163 (C++ filterFFT) as one call: y = irfft(rfft(s, n) * H)
 template<typename T>

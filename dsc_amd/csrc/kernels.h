@@ -201,6 +201,16 @@ void dsc_launch_conv_crop(const void *frames, void *y, long long q0, long long n
 // out[i] = in[n - 1 - i] (fft_conv.hip)
 void dsc_launch_reverse(const void *in, void *out, int n, bool single_precision, hipStream_t stream);
 
+// ---- 2-D transforms of small images (dsc_fft2 / dsc_ifft2 / dsc_rfft2, fft2.cpp) -----------------
+// One pass (fft_2d.hip): in [n_img][h][w] (complex for C2C, reals for R2C_CAST and R2C_PACKED), zero padded / cropped to N0 x N1,
+// out [n_img][N0][N1] complex (R2C_PACKED: [n_img][N0][N1/2 + 1]).  N0, N1 in {32, 64, 128} (R2C_PACKED: N1 in {64, 128, 256}).
+// A workgroup owns dsc_fft2_regs_group() images and addresses them with 31-bit byte offsets: group * h * w * element size < 0x7f000000
+// is the caller's to check.  in == out is allowed for C2C with h == N0 and w == N1.
+bool dsc_fft2_regs_supports(int N0, int N1, dsc_fft_mode mode);
+int dsc_fft2_regs_group(int N0, int N1, dsc_fft_mode mode, bool single_precision);
+void dsc_launch_fft2_regs(const void *in, void *out, long long n_img, int N0, int N1, int h, int w, dsc_fft_mode mode, bool inverse,
+                          bool single_precision, double scale, hipStream_t stream);
+
 // ---- element-wise ------------------------------------------------------------------------
 // dtype codes are dsc_dtype values (0 f32, 1 f64, 2 c32, 3 c64)
 void dsc_launch_cast(const void *in, int in_dtype, void *out, int out_dtype, long long ne, hipStream_t stream);

@@ -396,6 +396,30 @@ def irfft(x: Tensor, out=None, n: int = -1, axis: int = -1) -> Tensor:
     return _fft_like(B.dsc_irfft, x, out, n, axis)
 
 
+# ---- 2-D transforms over the last two axes (include/dsc_mi355x.h, Section F): numpy.fft.fft2 / ifft2 / rfft2 / irfft2 with
+# s = (n0, n1) rounded up to powers of two; None = the axis lengths (irfft2: n1 counts bins, like irfft's n)
+
+def _fft2_like(f, x: Tensor, out, s) -> Tensor:
+    n0, n1 = (-1, -1) if s is None else s
+    return Tensor(f(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), int(n0), int(n1)), out is not None)
+
+
+def fft2(x: Tensor, out=None, s=None) -> Tensor:
+    return _fft2_like(B.dsc_fft2, x, out, s)
+
+
+def ifft2(x: Tensor, out=None, s=None) -> Tensor:
+    return _fft2_like(B.dsc_ifft2, x, out, s)
+
+
+def rfft2(x: Tensor, out=None, s=None) -> Tensor:
+    return _fft2_like(B.dsc_rfft2, x, out, s)
+
+
+def irfft2(x: Tensor, out=None, s=None) -> Tensor:
+    return _fft2_like(B.dsc_irfft2, x, out, s)
+
+
 def filter_fft(s: Tensor, H: Tensor, out=None) -> Tensor:
     """irfft(rfft(s, n) * H) with n = 2 * (len(H) - 1), fused where a kernel exists."""
     return Tensor(B.dsc_filter_fft(_get_ctx(), s._c_ptr, H._c_ptr, _c_ptr_or_none(out)), out is not None)

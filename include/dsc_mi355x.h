@@ -296,6 +296,32 @@ dsc_tensor *dsc_convolve(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h,
 dsc_tensor *dsc_correlate(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h, int mode, dsc_tensor *out);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section F — 2-D transforms (no reference counterpart).
+ *
+ * numpy.fft.fft2 / ifft2 / rfft2 / irfft2 over the LAST TWO axes (n0 belongs to axis -2, n1 to axis -1); leading axes are batch;
+ * 2 <= n_dim <= 4.  Each call is DEFINED as a composition of the 1-D operators, so their shape rules (rounding to a power of
+ * two, zero padding / cropping, n <= 0 = the axis length, irfft's bin rule) carry over unchanged:
+ *   dsc_fft2  (x, n0, n1) = dsc_fft  (dsc_fft  (x, n1, -1), n0, -2)   complex [.., N0, N1]; real input widened as dsc_fft does
+ *   dsc_ifft2 (x, n0, n1) = dsc_ifft (dsc_ifft (x, n1, -1), n0, -2)   the same, scaled 1 / (N0 N1)
+ *   dsc_rfft2 (x, n0, n1) = dsc_fft  (dsc_rfft (x, n1, -1), n0, -2)   x real; complex [.., N0, N1/2 + 1]
+ *   dsc_irfft2(X, n0, n1) = dsc_irfft(dsc_ifft (X, n0, -2), n1, -1)   X complex [.., h, b]; real [.., N0, 2 order],
+ *                           order = pow2((n1 > 0 ? n1 : b) - 1); the imaginary parts of columns 0 and `order` of the
+ *                           intermediate are dropped, as dsc_irfft drops them
+ * with N0 = pow2(n0 > 0 ? n0 : h), N1 = pow2(n1 > 0 ? n1 : w).  On power-of-two shapes these equal numpy's with s = (N0, N1).
+ * out: NULL or a tensor of the result's shape and dtype; for dsc_fft2 / dsc_ifft2 of complex input with h == N0 and w == N1, out
+ * may be x itself (in place), on every route.  Argument errors print and exit like every operator.
+ * dsc_last_fft_path: "fft2_regs" / "rfft2_regs" — ONE pass, the image resident in registers (fft_2d.hip): fft2 / ifft2 with
+ * N0, N1 in {32, 64, 128}, rfft2 with N0 in {32, 64, 128} and N1 in {64, 128, 256}; needs no intermediate — or "fft2_composed" /
+ * "rfft2_composed" / "irfft2_composed": the two 1-D operators in turn with an arena intermediate that is freed before returning
+ * (every other size, DSC_NO_FFT2_FUSED=1, images too large for the fused kernel's 31-bit buffer offsets).  dsc_irfft2 is NOT
+ * fused: it always runs composed.
+ */
+dsc_tensor *dsc_fft2  (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n0, int n1);
+dsc_tensor *dsc_ifft2 (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n0, int n1);
+dsc_tensor *dsc_rfft2 (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n0, int n1);
+dsc_tensor *dsc_irfft2(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n0, int n1);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
