@@ -176,6 +176,8 @@ dsc_fft2 = _sig('dsc_fft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c
 dsc_ifft2 = _sig('dsc_ifft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
 dsc_rfft2 = _sig('dsc_rfft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
 dsc_irfft2 = _sig('dsc_irfft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
+dsc_hilbert = _sig('dsc_hilbert', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
+dsc_envelope = _sig('dsc_envelope', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

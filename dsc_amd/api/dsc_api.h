@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate` and `dsc::fft2 / ifft2 / rfft2 / irfft2`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` and `dsc::hilbert / envelope`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -258,6 +258,13 @@ template<typename T>
 static inline tensor<T> convolve(const tensor<T> &x, const tensor<T> &h, int mode = 0) noexcept { return dsc_convolve(ctx, x.x_, h.x_, mode, nullptr); }
 template<typename T>
 static inline tensor<T> correlate(const tensor<T> &x, const tensor<T> &h, int mode = 2) noexcept { return dsc_correlate(ctx, x.x_, h.x_, mode, nullptr); }
+
+// Section G of dsc_mi355x.h: analytic signal along the last axis (scipy.signal.hilbert(x, N) — complex payload, like rfft<T> — and its
+// absolute value); n <= 0: the row length, rounded up to a power of two
+template<typename T>
+static inline tensor<T> hilbert(const tensor<T> &x, int n = -1) noexcept { return dsc_hilbert(ctx, x.x_, nullptr, n); }
+template<typename T>
+static inline tensor<T> envelope(const tensor<T> &x, int n = -1) noexcept { return dsc_envelope(ctx, x.x_, nullptr, n); }
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

@@ -632,6 +632,20 @@ template<typename R> struct conv_frames {
     int D, T_out;
 };
 
+// Analytic signal (dsc_hilbert / dsc_envelope, the fused route).  The rows of s go through the filter with the CONSTANT response
+// H[0] = H[L] = 0, H[k] = -i (0 < k < L): no H is loaded.  After the inverse passes the thread fetches the sample pair (x[2k], x[2k+1]) of
+// its row again and stores to out (y unused): ENV = false the complex pairs (x, y) of [n_lines][2L] complex rows, ENV = true their
+// moduli, [n_lines][2L] reals.
+template<typename R, bool ENV> struct hilbert_rows {
+    void *out;
+};
+template<typename... SRC> struct filter_src { static constexpr bool conv = false, hilbert = false, envelope = false; };
+template<typename R> struct filter_src<conv_frames<R>> { static constexpr bool conv = true, hilbert = false, envelope = false; };
+template<typename R, bool ENV> struct filter_src<hilbert_rows<R, ENV>> { static constexpr bool conv = false, hilbert = true, envelope = ENV; };
+
+__device__ __forceinline__ float modulus(float re, float im) { return sqrtf((re * re) + (im * im)); }       // dsc_abs of a complex value (elementwise.hip)
+__device__ __forceinline__ double modulus(double re, double im) { return sqrt((re * re) + (im * im)); }
+
 template<int POL>
 __device__ __forceinline__ void buf_store_real(float a, __amdgpu_buffer_rsrc_t r, int voff) {
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, a), r, voff, 0, POL);
@@ -647,12 +661,13 @@ __device__ __forceinline__ void buf_store_real(double a, __amdgpu_buffer_rsrc_t 
 // in the same thread, one staging round trip to bring the pairs back to the load layout, inverse passes: the spectrum
 // never leaves the CU.  s rows may be shorter than 2L (zero padded) or longer (cropped).
 // SRC: empty (the rows of s), or conv_frames<R> (s, y, in_pitch_b and in_len_b unused): overlap-save blocks in, the linear part of each
-// out.  An empty pack leaves the kernel's signature and code as they are without frames.
+// out.  An empty pack leaves the kernel's signature and code as they are without frames.  hilbert_rows<R, ENV> (H and y unused): the rows
+// of s as without a pack, the constant response of the analytic signal in place of H, and the store described there.
 template<typename R, int B, bool TWO, typename... SRC>
 __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>::WAVES_PER_EU)) void fft_mid_filter_kernel(
     const R *__restrict__ s, const cpx<R> *__restrict__ H, cpx<R> *__restrict__ y, long long n_lines, const cpx<R> *__restrict__ tw_full,
     const cpx<R> *__restrict__ tw_real, int in_pitch_b, int in_len_b, SRC... frames) {
-    constexpr bool FRAMES = sizeof...(SRC) != 0;
+    constexpr bool FRAMES = filter_src<SRC...>::conv, HILBERT = filter_src<SRC...>::hilbert, ENVELOPE = filter_src<SRC...>::envelope;
     const auto fr = frames_of(frames...);
     using C = cpx<R>;
     using cfg = mid_cfg<R, B, TWO, 1>;
@@ -674,9 +689,20 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
     }();
     const __amdgpu_buffer_rsrc_t rout = [&] {
         if constexpr (FRAMES) return __builtin_amdgcn_make_buffer_rsrc((void *) fr.y, 0, fr.y_bytes, 0x00020000);
+        else if constexpr (HILBERT) {
+            // the group's rows of out: 2L complex (ENV: 2L reals) each — G 2L complex are at most 1 MiB, far inside the 31-bit offsets
+            constexpr int OB = (ENVELOPE ? 1 : 2) * L * CB;
+            static_assert((long long) G * OB < 0x7f000000LL, "31-bit byte offsets");
+            return __builtin_amdgcn_make_buffer_rsrc((void *) ((char *) fr.out + line0 * OB), 0, n_valid * OB, 0x00020000);
+        }
         else return __builtin_amdgcn_make_buffer_rsrc((void *) (y + line0 * L), 0, n_valid * L * CB, 0x00020000);
     }();
-    const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void *) H, 0, (L + 1) * CB, 0x00020000);
+    [[maybe_unused]] const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void *) H, 0, HILBERT ? 0 : (L + 1) * CB, 0x00020000);
+    // a bin of the spectrum times H (its byte offset: voff + soff); the analytic signal's -i is a swap and a sign, and rh is dead
+    auto times_h = [&](C xk, int voff, int soff) -> C {
+        if constexpr (HILBERT) return C{xk.y, -xk.x};
+        else return cmul(xk, buf_load<kCached>(rh, voff, soff, R{}));
+    };
     const int vin = g * in_pitch_b + t * CB, vout = (g * L + t) * CB;
     R *stage = plane + g * SP;
     for (int i = tid; i < cfg::TABLE; i += NT) wtab[i] = tw_full[(long long) i * cfg::TABLE_STRIDE];
@@ -736,9 +762,10 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
             C xk = C{(R) 0.5 * sx + wdx, (R) 0.5 * sy + wdy};
             C xm = C{(R) 0.5 * sx - wdx, wdy - (R) 0.5 * sy};
             if (m == 0 && t == 0) { xk.y = (R) 0; xm.y = (R) 0; }
-            C a = cmul(xk, buf_load<kCached>(rh, t * CB, T * m * CB, R{}));
-            C b = cmul(xm, buf_load<kCached>(rh, hm_voff, T * (15 - m) * CB, R{}));
+            C a = times_h(xk, t * CB, T * m * CB);
+            C b = times_h(xm, hm_voff, T * (15 - m) * CB);
             if (m == 0 && t == 0) { a.y = (R) 0; b.y = (R) 0; }                         // dsc_fft.h:227-228: real parts only at k = 0, L
+            if (HILBERT && m == 0 && t == 0) { a.x = (R) 0; b.x = (R) 0; }              // H[0] = H[L] = 0
             // inverse: Z'[k] = s/2 + wq' d, Z'[L-k] = conj(s/2 - wq' d), wq' = (i/2) conj(w)  (dsc_fft.h:194-228)
             sx = a.x + b.x; sy = a.y - b.y; dx = a.x - b.x; dy = a.y + b.y;
             wqx = (R) 0.5 * w.y; wqy = (R) 0.5 * w.x;
@@ -750,7 +777,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
             }
         }
         if (t == 0) {                                                     // k = L/2: X = conj Z, then Z' = conj(X H): slot 0, nobody's partner
-            const C ym = cmul(C{zm0.x, -zm0.y}, buf_load<kCached>(rh, (L / 2) * CB, 0, R{}));
+            const C ym = times_h(C{zm0.x, -zm0.y}, (L / 2) * CB, 0);
             stage[0] = ym.x;
             stage[L / 2] = -ym.y;
         }
@@ -799,9 +826,10 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
             C xm = C{(R) 0.5 * sx - wdx, wdy - (R) 0.5 * sy};
             if (i == 0 && t == 0) { xk.y = (R) 0; xm.y = (R) 0; }
             // times the filter
-            C a = cmul(xk, buf_load<kCached>(rh, t * CB, T * i * CB, R{}));
-            C b = cmul(xm, buf_load<kCached>(rh, hm_voff, T * (15 - i) * CB, R{}));
+            C a = times_h(xk, t * CB, T * i * CB);
+            C b = times_h(xm, hm_voff, T * (15 - i) * CB);
             if (i == 0 && t == 0) { a.y = (R) 0; b.y = (R) 0; }                         // dsc_fft.h:227-228: real parts only at k = 0, L
+            if (HILBERT && i == 0 && t == 0) { a.x = (R) 0; b.x = (R) 0; }              // H[0] = H[L] = 0
             // inverse: Z'[k] = s/2 + wq' d, Z'[L-k] = conj(s/2 - wq' d), wq' = (i/2) conj(w)  (dsc_fft.h:194-228)
             sx = a.x + b.x; sy = a.y - b.y; dx = a.x - b.x; dy = a.y + b.y;
             wqx = (R) 0.5 * w.y; wqy = (R) 0.5 * w.x;
@@ -813,7 +841,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
         }
         if (t == 0) {                                                         // k = L/2: X = conj Z, then Z' = conj(X H); after the loop: its
             const R ay = stage[L / 2];                                        // slot is nobody's pair (T * 16 = L/2 belongs to i = 16)
-            const C ym = cmul(C{amx, -ay}, buf_load<kCached>(rh, (L / 2) * CB, 0, R{}));
+            const C ym = times_h(C{amx, -ay}, (L / 2) * CB, 0);
             zmid = C{ym.x, -ym.y};
             stage[L / 2] = zmid.x;
         }
@@ -868,6 +896,48 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
                     }
                 }
             }
+    } else if constexpr (HILBERT) {
+        // v[i B + p] = (y[2k], y[2k + 1]), k = (t + T i) + COLS brev(p).  The sample pair (x[2k], x[2k + 1]) of the row comes from memory a
+        // second time, under the rule of the first load: a pair past the row's valid bytes reads zero (the descriptor spans the group's
+        // rows, so the offset is pushed out of its range), a pair cut by an odd length keeps its first sample.
+        // These are the addresses of the first load (the same thread owns the same pairs at both ends), and left alone the compiler keeps
+        // all 32 pairs in registers from there to here.  That is the better form only where the registers are there (KEEP_X: f32 lines of
+        // 8192 and 16384 points, -11 .. -15 %; f64 lines of 1024 .. 4096 points, -4 .. -7 %, and of 8192 points for the complex store,
+        // -7 %): elsewhere it spills or costs a wave per SIMD (f32 lines of 2048 points: +26 %), and the load goes through an opaque
+        // copy of the thread's offset, i.e. is made again.  It then misses the L2 (FETCH_SIZE x1.9 of the plain filter's,
+        // profiles/hilbert_trace.md) and is served past it.  tools/bench_hilbert.py on both builds, DESIGN 4.8.
+#if defined(DSC_HILBERT_KEEP_X)         // (A/B switches)
+        constexpr bool KEEP_X = true;
+#elif defined(DSC_HILBERT_REREAD_X)
+        constexpr bool KEEP_X = false;
+#else
+        constexpr bool KEEP_X = sizeof(R) == 4 ? (!TWO && B >= 8) : ((TWO && B == 32) || (!TWO && (B <= 4 || (B == 8 && !ENVELOPE))));
+#endif
+        int vin2 = vin;
+        if constexpr (!KEEP_X) asm volatile("" : "+v"(vin2));
+        const int vout2 = ENVELOPE ? vout : 2 * vout;
+        // NB pairs (16 registers) at a time, each batch fenced: all 32 in flight at once cost the two-pass f64 lines 70 spilled registers
+        constexpr int NB = 32 / (int) sizeof(R);
+        auto pair_of = [](int q) constexpr { return T * (q / B) + COLS * brev(q % B, LOGB); };      // k - t of register q = i B + p
+#pragma unroll
+        for (int q0 = 0; q0 < 32; q0 += NB) {
+            C xs[NB];
+#pragma unroll
+            for (int m = 0; m < NB; ++m) {
+                constexpr int kOut = 0x7f000000;
+                const int kk = pair_of(q0 + m), eoff = (kk + t) * CB;
+                xs[m] = buf_load<kCached>(rin, eoff < in_len_b ? vin2 : kOut, kk * CB, R{});
+                if (eoff + CB > in_len_b) xs[m].y = (R) 0;
+            }
+#pragma unroll
+            for (int m = 0; m < NB; ++m) {
+                const int kk = pair_of(q0 + m);
+                const C r = C{v[q0 + m].x * scale, v[q0 + m].y * scale};
+                if constexpr (ENVELOPE) buf_store<kStream>(C{modulus(xs[m].x, r.x), modulus(xs[m].y, r.y)}, rout, vout2, kk * CB);
+                else                    buf_store_pair<kStream>(C{xs[m].x, r.x}, C{xs[m].y, r.y}, rout, vout2, 2 * kk * CB);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
     } else {
 #pragma unroll
         for (int i = 0; i < CPT; ++i)
@@ -1314,7 +1384,50 @@ void launch_conv_len(int L, const void *H, long long n_lines, const void *tw_ful
     }
 }
 
+template<typename R, int B, bool TWO, bool ENV>
+void launch_hilbert(const void *x, void *out, long long n_lines, const void *tw_full, const void *tw_real, int in_pitch_b, int in_len_b,
+                    hipStream_t stream) {
+    using cfg = mid_cfg<R, B, TWO, 1>;
+    constexpr size_t lds = mid_lds_bytes<R, B, TWO, 1>();
+    static unsigned long long attr_devices = 0;
+    if (dsc_first_use_on_device(attr_devices)) {
+        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_filter_kernel<R, B, TWO, hilbert_rows<R, ENV>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+    }
+    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
+    DSC_LAUNCH((fft_mid_filter_kernel<R, B, TWO, hilbert_rows<R, ENV>>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, (const R *) x, nullptr,
+               nullptr, n_lines, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, in_pitch_b, in_len_b, hilbert_rows<R, ENV>{out});
+}
+
+template<typename R, bool ENV>
+void launch_hilbert_len(int L, const void *x, void *out, long long n_lines, const void *tw_full, const void *tw_real, int pb, int lb, hipStream_t stream) {
+    switch (L) {
+        case 256:   launch_hilbert<R, 8, true, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+        case 512:   launch_hilbert<R, 16, true, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+        case 1024:  launch_hilbert<R, 32, true, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+        case 2048:  launch_hilbert<R, 2, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+        case 4096:  launch_hilbert<R, 4, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+        case 8192:  launch_hilbert<R, 8, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+        default:    launch_hilbert<R, 16, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
+    }
+}
+
 }  // namespace
+
+bool dsc_hilbert_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n - 1)) == 0; }
+
+// Fused analytic signal (dsc_hilbert / dsc_envelope): see hilbert_rows and kernels.h.
+void dsc_launch_hilbert_regs(const void *x, void *out, long long n_lines, int n, bool envelope, bool single_precision, const void *tw_full,
+                             const void *tw_real, long long in_pitch, int in_len, hipStream_t stream) {
+    if (n_lines <= 0) return;
+    const int rb = single_precision ? 4 : 8, pb = (int) (in_pitch * rb), lb = in_len * rb;
+    if (single_precision) {
+        if (envelope) launch_hilbert_len<float, true>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
+        else          launch_hilbert_len<float, false>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
+    } else {
+        if (envelope) launch_hilbert_len<double, true>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
+        else          launch_hilbert_len<double, false>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
+    }
+}
 
 bool dsc_conv_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n - 1)) == 0; }
 

@@ -201,6 +201,25 @@ void dsc_launch_conv_crop(const void *frames, void *y, long long q0, long long n
 // out[i] = in[n - 1 - i] (fft_conv.hip)
 void dsc_launch_reverse(const void *in, void *out, int n, bool single_precision, hipStream_t stream);
 
+// ---- analytic signal (dsc_hilbert / dsc_envelope, hilbert.cpp) ----------------------------------
+// Fused route (fft_regs_mid.hip), n = 512 .. 32768: row q of x = [n_lines][in_pitch] reals, of which in_len <= n are used and the rest
+// reads as zero, through y = irfft(rfft(row, n) * H) with the constant H[0] = H[n/2] = 0, H[k] = -i otherwise; out = [n_lines][n] complex
+// (row, y), or with `envelope` [n_lines][n] reals sqrt(row^2 + y^2).  Tables of the n/2-point REAL plan.  A workgroup addresses its rows
+// of x with 31-bit byte offsets: 64 in_pitch elem < 2^30 is the caller's to check.  out must not overlap x (x is read twice).
+bool dsc_hilbert_regs_supports(int n);
+void dsc_launch_hilbert_regs(const void *x, void *out, long long n_lines, int n, bool envelope, bool single_precision, const void *tw_full,
+                             const void *tw_real, long long in_pitch, int in_len, hipStream_t stream);
+// The composed route's small kernels (fft_hilbert.hip).  H [n/2 + 1] complex <- the constant response above.
+void dsc_launch_hilbert_response(void *H, int n, bool single_precision, hipStream_t stream);
+// out rows q0 .. q0 + n_lines - 1 <- rows q0 .. of x [..][in_pitch] (in_len used, zero padded to n) zipped with y [n_lines][n] reals:
+// complex pairs (x, y) of out [..][n] complex, or with `envelope` sqrt(x^2 + y^2) of out [..][n] reals.  y_double (f32 x and out only):
+// y is f64, the modulus is taken in f64, and the result is rounded once
+void dsc_launch_hilbert_zip(const void *x, const void *y, void *out, long long q0, long long n_lines, int n, long long in_pitch, int in_len,
+                            bool envelope, bool single_precision, bool y_double, hipStream_t stream);
+// xw [n_lines][wpitch] f64 <- samples j < in_len of rows q0 .. of x [..][in_pitch] f32, zero from in_len on; wpitch even, >= in_len
+void dsc_launch_hilbert_widen(const void *x, void *xw, long long q0, long long n_lines, long long in_pitch, int in_len, int wpitch,
+                              hipStream_t stream);
+
 // ---- 2-D transforms of small images (dsc_fft2 / dsc_ifft2 / dsc_rfft2, fft2.cpp) -----------------
 // One pass (fft_2d.hip): in [n_img][h][w] (complex for C2C, reals for R2C_CAST and R2C_PACKED), zero padded / cropped to N0 x N1,
 // out [n_img][N0][N1] complex (R2C_PACKED: [n_img][N0][N1/2 + 1]).  N0, N1 in {32, 64, 128} (R2C_PACKED: N1 in {64, 128, 256}).

@@ -420,6 +420,23 @@ def irfft2(x: Tensor, out=None, s=None) -> Tensor:
     return _fft2_like(B.dsc_irfft2, x, out, s)
 
 
+# ---- analytic signal along the last axis (include/dsc_mi355x.h, Section G): scipy.signal.hilbert(x, N) and its absolute value, N = n (None
+# or <= 0: the row length) rounded up to a power of two; rows are cropped or zero padded to N
+
+def _hilbert_like(f, x: Tensor, n, out) -> Tensor:
+    return Tensor(f(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), -1 if n is None else int(n)), out is not None)
+
+
+def hilbert(x: Tensor, n: Union[int, None] = -1, out: Union[Tensor, None] = None) -> Tensor:
+    """Analytic signal x + i H{x} of every row of real x [.., T]: complex [.., N] whose real part is the (padded / cropped) row."""
+    return _hilbert_like(B.dsc_hilbert, x, n, out)
+
+
+def envelope(x: Tensor, n: Union[int, None] = -1, out: Union[Tensor, None] = None) -> Tensor:
+    """|hilbert(x, n)|, real [.., N] of x's dtype, without the complex intermediate."""
+    return _hilbert_like(B.dsc_envelope, x, n, out)
+
+
 def filter_fft(s: Tensor, H: Tensor, out=None) -> Tensor:
     """irfft(rfft(s, n) * H) with n = 2 * (len(H) - 1), fused where a kernel exists."""
     return Tensor(B.dsc_filter_fft(_get_ctx(), s._c_ptr, H._c_ptr, _c_ptr_or_none(out)), out is not None)

@@ -322,6 +322,28 @@ dsc_tensor *dsc_rfft2 (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n
 dsc_tensor *dsc_irfft2(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n0, int n1);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section G — analytic signal (no reference counterpart).
+ *
+ * Along the LAST axis of x real [.., T] (f32 or f64, at most 4 dims); other axes: transpose first.  N = pow2(n > 0 ? n : T), the
+ * length rule of dsc_fft; N >= 2.  Each row is cropped or zero padded to N samples (x_used), and with H[0] = H[N/2] = 0 and
+ * H[k] = -i for 0 < k < N/2
+ *   y = dsc_irfft(dsc_rfft(x_used, N) * H, N)
+ *   dsc_hilbert (x, n) = x_used + i y            complex [.., N] (c32 / c64); the real part is a bit-for-bit copy of x_used
+ *   dsc_envelope(x, n) = sqrt(x_used^2 + y^2)    real [.., N] of x's dtype, the formula of dsc_abs
+ * On power-of-two rows dsc_hilbert is scipy.signal.hilbert(x, N) and dsc_envelope its absolute value.
+ * out: NULL or a tensor of the result's shape and dtype; it must not share memory with x.  Argument errors (complex input, N < 2,
+ * a wrong out) print and exit like every operator.
+ * dsc_last_fft_path: "hilbert_regs" / "envelope_regs" — ONE pass for N = 512 .. 32768: the fused filter kernel with the constant H
+ * (nothing loaded for it) stores the complex pairs or their moduli; needs no scratch — or "hilbert_composed" /
+ * "envelope_composed": H written into scratch, rows in chunks through dsc_filter_fft into a scratch chunk, then zipped with x into
+ * out (every other N, rows too long for the fused kernel's 31-bit buffer offsets, DSC_NO_HILBERT_FUSED=1; the switch is read at
+ * every call).  On that route f32 rows of N >= 131072 are widened to f64 for the filter and y is rounded to f32 once: an f32
+ * transform of that length cannot hold the operator's error bound on rows whose energy sits in a few samples.
+ */
+dsc_tensor *dsc_hilbert (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n);
+dsc_tensor *dsc_envelope(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
