@@ -23,7 +23,8 @@
 //
 // In-register DFTs are radix-2 DIF with compile-time twiddles (output index bit-reversed in
 // the register number, which is free: every register index is a constant).  Inter-pass
-// twiddles come from an 8 KiB LDS table (W_1024) and two per-thread constants.
+// twiddles come from an 8 KiB LDS table indexed by the two factors of the exponent,
+// T[r][h] = W_1024^{r h} (r = register, a constant; h = per-thread), and two per-thread constants.
 // The inverse kernel (dsc_irfft, dsc_fft.h:194-236) is the same pipeline run backwards.
 #include "kernels.h"
 
@@ -50,7 +51,7 @@ __device__ __forceinline__ f2 to_f2(cf a) { return f2{a.x, a.y}; }
 constexpr int kM = 32768;            // complex points per row
 constexpr int kRowPitch = 34;        // floats per LDS row: 32 + 2 -> conflict-free b64 row reads
 constexpr int kPlaneFloats = 1024 * kRowPitch;
-constexpr int kLdsBytes = kPlaneFloats * 4 + 1024 * 8;      // exchange plane + W_1024 table
+constexpr int kLdsBytes = kPlaneFloats * 4 + 1024 * 8;      // exchange plane + twiddle table T
 constexpr int kTabEntries = 1024;
 
 // aux table layout (f2 entries): [0,1024) W_1024^m | [1024,2048) W_32768^m | [2048,3072) W_65536^m
@@ -220,22 +221,48 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 // own row of 32 as 16 x b64.  Two base registers cover all 32 slots with 16-bit immediates.
 template<int COMP>
 __device__ __forceinline__ void plane_write(float *plane, int wbase, const cf (&v)[32]) {
+    // The second base is opaque: left to itself the compiler folds it back into the first, finds the offsets of slots 16..31
+    // beyond the 16-bit immediate and builds one address per write (16 v_add_u32 and 16 unpaired ds_write_b32 per plane).
+    // With two bases every slot is base + slot' * 4352 B, slot' < 16: all 32 writes pair into ds_write2st64_b32 (17 slot' <= 255);
+    // 0.837-0.842 -> 0.830-0.838 ms on the rfft kernel.
+    int wbase_hi = wbase + 16 * (32 * kRowPitch);
+    asm("" : "+v"(wbase_hi));
     float *lo16 = plane + wbase;
-    float *hi16 = lo16 + 16 * (32 * kRowPitch);
+    float *hi16 = plane + wbase_hi;
+    // even registers hold slots 0..15, odd ones slots 16..31: one base at a time (writes through the other base, whose
+    // distance the compiler cannot see, would stand between the two halves of a pair)
 #pragma unroll
-    for (int p = 0; p < 32; ++p) {
-        const int slot = br5(p);
-        const float val = COMP == 0 ? v[p].x : v[p].y;
-        if (slot < 16) lo16[slot * (32 * kRowPitch)] = val;
-        else           hi16[(slot - 16) * (32 * kRowPitch)] = val;
-    }
+    for (int p = 0; p < 32; p += 2) lo16[br5(p) * (32 * kRowPitch)] = COMP == 0 ? v[p].x : v[p].y;
+#pragma unroll
+    for (int p = 1; p < 32; p += 2) hi16[(br5(p) - 16) * (32 * kRowPitch)] = COMP == 0 ? v[p].x : v[p].y;
 }
+
+// One 8-byte LDS read that stays one ds_read_b64.  hipcc fuses neighbouring 8-byte reads of one base into ds_read2_b64,
+// which moves half as much per clock (tools/ldsbench.hip: 4.15 against 2.40 cycles per wave and 8 B/lane), and the row
+// reads of a plane sit between two barriers with nothing to hide behind: 0.830-0.838 -> 0.820-0.823 ms on the rfft kernel
+// (profiles/lds_read_forms_64k.md).  The access is volatile IN the LDS address space (a generic volatile pointer would turn
+// it into a flat load); the compiler counts it in lgkmcnt like any other LDS read.  The twiddle table reads do NOT go through
+// here: they are interleaved with arithmetic and with the plane writes, where the fixed order of volatile accesses costs
+// more (0.827-0.829 ms) than the fused reads do.
+#ifndef DSC_LDS_SPLIT_READS
+#define DSC_LDS_SPLIT_READS 1
+#endif
+__device__ __forceinline__ f2 lds_read_b64(const f2 *p) {
+#if DSC_LDS_SPLIT_READS
+    return *(const volatile __attribute__((address_space(3))) f2 *) p;
+#else
+    return *p;
+#endif
+}
+
+// Row and column numbers are far below 2^24: their products with the pitch (here and in three_passes) take the full-rate
+// 24-bit multiply; v_mul_lo_u32 issues at a quarter of the rate.
 template<int COMP>
 __device__ __forceinline__ void plane_read(const float *plane, int row, cf (&v)[32]) {
-    const f2 *r = (const f2 *) (plane + row * kRowPitch);
+    const f2 *r = (const f2 *) (plane + __mul24(row, kRowPitch));
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
-        const f2 t = r[m];
+        const f2 t = lds_read_b64(r + m);
         if (COMP == 0) { v[2 * m].x = t.x; v[2 * m + 1].x = t.y; }
         else           { v[2 * m].y = t.x; v[2 * m + 1].y = t.y; }
     }
@@ -323,6 +350,17 @@ __device__ __forceinline__ void store_c(cf a, __amdgpu_buffer_rsrc_t r, int voff
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, to_f2(a)), r, voff, soff, POLICY);
 }
 
+// The inter-pass twiddle table.  Both twiddle loops of three_passes() need W_1024^{r h} with r the register number (a
+// constant, 1..31) and h a 5-bit per-thread value, so the table is laid out by the two factors: T[r][h] = W_1024^{r h}, 32 x 32
+// entries — the same 8 KiB and the same floats as a linear W_1024^m table, but every read is ONE per-thread base (8 h) plus an
+// immediate (256 r): no index arithmetic, and the 32 values of h a wave reads lie in consecutive entries (conflict free; the
+// linear table read at stride r was gcd(r, 32)-way conflicted).  Filled once per workgroup.
+__device__ __forceinline__ void fill_twiddle_table(f2 *T, const f2 *aux) {
+    const int t = threadIdx.x;
+    T[t] = aux[kAuxW1024 + (t >> 5) * (t & 31)];
+    __syncthreads();
+}
+
 // One LDS transpose = re plane, then im plane.  Barriers sit AFTER each read phase (not before
 // each write phase): a wave's LDS writes then overlap the tail of its own butterflies and
 // the other waves' arithmetic; the last one leaves the plane free for whoever writes next.
@@ -348,7 +386,7 @@ struct no_hook { __device__ __forceinline__ void operator()() const {} };
 // `before_pass3` runs between the second exchange and the last 32-point DFT: from there to the end of the row only v[] (64
 // VGPRs) is live, which leaves room to request part of the NEXT row that early (irfft64k_kernel does).
 template<bool INV, typename Hook = no_hook>
-__device__ __forceinline__ void three_passes(cf (&v)[32], float *plane, const f2 *w1024, const f2 *aux, int wave_sgpr,
+__device__ __forceinline__ void three_passes(cf (&v)[32], float *plane, const f2 *T, const f2 *aux, int wave_sgpr,
                                              bool mirrored_in, bool mirrored_out, Hook before_pass3 = Hook{}) {
     // ---- pass 1 (over the slow index) and twiddle W_1024^{hi r1}, hi = col >> 5
     dft32<INV>(v);
@@ -357,29 +395,31 @@ __device__ __forceinline__ void three_passes(cf (&v)[32], float *plane, const f2
         const int t = thread_id(wave_sgpr);
         const int col = mirrored_in ? column_of(t >> 6, t & 63) : t;
         const int hi = col >> 5;
+        const f2 *th = T + hi;                            // T[r1][hi]: hi takes two (mirrored: three) values per wave, the reads broadcast
 #pragma unroll
         for (int r1 = 1; r1 < 32; ++r1) {
-            const cf w = to_cf(w1024[hi * r1]);
+            const cf w = to_cf(th[32 * r1]);
             v[br5(r1)] = INV ? cmul_conj(v[br5(r1)], w) : cmul(v[br5(r1)], w);
         }
         // exchange 1: (hi, lo)[r1] -> thread (r1, lo), registers [hi];  LDS row = r1*32 + lo, col = hi
-        exchange(plane, (col & 31) * kRowPitch + hi, t, v, u);
+        exchange(plane, __mul24(col & 31, kRowPitch) + hi, t, v, u);
     }
     // ---- pass 2 (over the middle index) and twiddle W_32768^{lo r1} W_1024^{lo r2}
     dft32<INV>(u);
     {
         const int t = thread_id(wave_sgpr);
         const int hi = t >> 5, lo = t & 31;              // (r1, lo)
-        const cf tw2_base = to_cf(aux[kAuxW32768 + hi * lo]);
+        const cf tw2_base = to_cf(aux[kAuxW32768 + __mul24(hi, lo)]);
         u[0] = INV ? cmul_conj(u[0], tw2_base) : cmul(u[0], tw2_base);
+        const f2 *tl = T + lo;                            // T[r2][lo]: the lanes read consecutive entries
 #pragma unroll
         for (int r2 = 1; r2 < 32; ++r2) {
-            const cf w = cmul(tw2_base, to_cf(w1024[lo * r2]));
+            const cf w = cmul(tw2_base, to_cf(tl[32 * r2]));
             u[br5(r2)] = INV ? cmul_conj(u[br5(r2)], w) : cmul(u[br5(r2)], w);
         }
         // exchange 2: (r1, lo)[r2] -> output column r1 + 32 r2, registers [lo];  LDS row = column
         const int col_out = mirrored_out ? column_of(t >> 6, t & 63) : t;
-        exchange(plane, hi * kRowPitch + lo, col_out, u, v);
+        exchange(plane, __mul24(hi, kRowPitch) + lo, col_out, u, v);
     }
     before_pass3();
     // ---- pass 3 (over the fast index)
@@ -414,9 +454,8 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
                                                        const f2 *__restrict__ aux, int in_pitch, int in_len PROBE_ARGS) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *plane = lds;
-    f2 *w1024 = (f2 *) (lds + kPlaneFloats);
-    w1024[threadIdx.x] = aux[kAuxW1024 + threadIdx.x];
-    __syncthreads();
+    f2 *T = (f2 *) (lds + kPlaneFloats);
+    fill_twiddle_table(T, aux);
 
     const int wave_sgpr = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
@@ -443,7 +482,7 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
         const __amdgpu_buffer_rsrc_t rout =
             __builtin_amdgcn_make_buffer_rsrc((void *) (X + (size_t) row * (kM + 1)), 0, (kM + 1) * 8 * IO_ON, 0x00020000);
 
-        three_passes<false>(v, plane, w1024, aux, wave_sgpr, false, true);     // v[p] = Z[k' + 1024 br5(p)]
+        three_passes<false>(v, plane, T, aux, wave_sgpr, false, true);     // v[p] = Z[k' + 1024 br5(p)]
         // (Requesting part of the next row before pass 3, as irfft64k_kernel does, was tried here too: it needs pass 3's results
         // pinned — the compiler otherwise sinks the butterflies into the post-pass and the merged region takes all 128
         // registers — and then fits 4 loads, which measured 0.842-0.849 ms against 0.845-0.849 ms: nothing.)
@@ -502,7 +541,7 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
         for (int m = 0; m < 8; ++m) {
             const int k = 2 * (t4 + 1024 * m) - skew;       // first bin of this lane's 16-B chunk
             if (m > 0 || k >= 0) {                          // only the row's first chunk can start before bin 0
-                const f2 lo2 = stage[k], hi2 = stage[k + 1];
+                const f2 lo2 = lds_read_b64(stage + k), hi2 = lds_read_b64(stage + k + 1);
                 const f4 q = f4{lo2.x, lo2.y, hi2.x, hi2.y};
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, q), rout, k * 8, 0, kStream);
             } else if (m == 0 && k == -1) {
@@ -525,7 +564,7 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
             if (m == 8 && wave != 0) break;                // bins past 32768 + 15 do not exist
             const int k = kM / 2 + 2 * (t4 + 1024 * m) - skew;
             if (m < 8 || k + 1 <= kM) {                     // only the row's last chunks can run past bin M
-                const f2 lo2 = stage[k - kStage2], hi2 = stage[k + 1 - kStage2];
+                const f2 lo2 = lds_read_b64(stage + k - kStage2), hi2 = lds_read_b64(stage + k + 1 - kStage2);
                 const f4 q = f4{lo2.x, lo2.y, hi2.x, hi2.y};
                 __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, q), rout, k * 8, 0, kStream);
             } else if (m == 8 && k == kM) {
@@ -602,7 +641,7 @@ __device__ __forceinline__ void staged_time_store(cf (&v)[32], float *plane, __a
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int k = 2 * (t4 + 1024 * m);
-        const f2 lo2 = stage[k], hi2 = stage[k + 1];
+        const f2 lo2 = lds_read_b64(stage + k), hi2 = lds_read_b64(stage + k + 1);
         const f4 q = f4{lo2.x, lo2.y, hi2.x, hi2.y};
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, q), rout, k * 8, 0, kStream);
         if (m & 1) __builtin_amdgcn_sched_barrier(0);
@@ -615,7 +654,7 @@ __device__ __forceinline__ void staged_time_store(cf (&v)[32], float *plane, __a
 #pragma unroll
     for (int m = 0; m < 8; ++m) {
         const int k = 2 * (t4 + 1024 * m);
-        const f2 lo2 = stage[k], hi2 = stage[k + 1];
+        const f2 lo2 = lds_read_b64(stage + k), hi2 = lds_read_b64(stage + k + 1);
         const f4 q = f4{lo2.x, lo2.y, hi2.x, hi2.y};
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, q), rout, (kM / 2 + k) * 8, 0, kStream);
         if (m & 1) __builtin_amdgcn_sched_barrier(0);
@@ -646,9 +685,8 @@ __global__ __launch_bounds__(1024) void irfft64k_kernel(const f2 *__restrict__ X
                                                         const f2 *__restrict__ aux, int in_pitch, int in_len PROBE_ARGS) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *plane = lds;
-    f2 *w1024 = (f2 *) (lds + kPlaneFloats);
-    w1024[threadIdx.x] = aux[kAuxW1024 + threadIdx.x];
-    __syncthreads();
+    f2 *T = (f2 *) (lds + kPlaneFloats);
+    fill_twiddle_table(T, aux);
 
     const int wave_sgpr = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 
@@ -688,7 +726,7 @@ __global__ __launch_bounds__(1024) void irfft64k_kernel(const f2 *__restrict__ X
         // the staging area, the rest after the second half.  (kEarly = 0: everything in the tail, as the forward kernel does.)
         constexpr int kEarly = DSC_IRFFT_EARLY_PAIRS;
         cf early[kEarly > 0 ? 2 * kEarly : 1];
-        three_passes<true>(v, plane, w1024, aux, wave_sgpr, true, false, [&]() {      // v[p] = z[t + 1024 br5(p)]
+        three_passes<true>(v, plane, T, aux, wave_sgpr, true, false, [&]() {      // v[p] = z[t + 1024 br5(p)]
             if constexpr (kEarly > 0) {
                 const int t3 = thread_id(wave_sgpr);
                 const int c3 = column_of(t3 >> 6, t3 & 63);
@@ -756,9 +794,8 @@ __global__ __launch_bounds__(1024) void filter64k_kernel(const float *__restrict
                                                          int in_len) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float *plane = lds;
-    f2 *w1024 = (f2 *) (lds + kPlaneFloats);
-    w1024[threadIdx.x] = aux[kAuxW1024 + threadIdx.x];
-    __syncthreads();
+    f2 *T = (f2 *) (lds + kPlaneFloats);
+    fill_twiddle_table(T, aux);
 
     const int wave_sgpr = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const __amdgpu_buffer_rsrc_t rh = __builtin_amdgcn_make_buffer_rsrc((void *) H, 0, (kM + 1) * 8, 0x00020000);
@@ -779,7 +816,7 @@ __global__ __launch_bounds__(1024) void filter64k_kernel(const float *__restrict
             (void *) (x + (size_t) next_row * in_pitch), 0, next_row < batch ? in_len * 4 : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rout =
             __builtin_amdgcn_make_buffer_rsrc((void *) (y + (size_t) row * 65536), 0, 65536 * 4, 0x00020000);
-        three_passes<false>(v, plane, w1024, aux, wave_sgpr, false, true);     // v[p] = Z[c + 1024 br5(p)]
+        three_passes<false>(v, plane, T, aux, wave_sgpr, false, true);     // v[p] = Z[c + 1024 br5(p)]
 
         // ---- post-pass, multiply by H, pre-pass: all on the pair (k, M-k) held by this lane.
         // In place: register br5(r) holds row r of the column before (Z) and after (Z'/M).
@@ -852,7 +889,7 @@ __global__ __launch_bounds__(1024) void filter64k_kernel(const float *__restrict
         // the next row's first kEarlyX loads are requested before the inverse transform's last pass (see irfft64k_kernel)
         constexpr int kEarlyX = DSC_FILTER_EARLY_LOADS;
         cf early[kEarlyX > 0 ? kEarlyX : 1];
-        three_passes<true>(z, plane, w1024, aux, wave_sgpr, true, false, [&]() {      // z[p] = y[2(t + 1024 br5(p)) .. +1]
+        three_passes<true>(z, plane, T, aux, wave_sgpr, true, false, [&]() {      // z[p] = y[2(t + 1024 br5(p)) .. +1]
             if constexpr (kEarlyX > 0) {
                 const int off = thread_id(wave_sgpr) * 8;
 #pragma unroll
