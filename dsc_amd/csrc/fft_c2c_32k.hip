@@ -42,7 +42,7 @@ __global__ __launch_bounds__(1024) void c2c32k_kernel(const f2 *__restrict__ z, 
         const __amdgpu_buffer_rsrc_t rnext = __builtin_amdgcn_make_buffer_rsrc(
             (void *) ((const char *) z + (size_t) next_row * in_pitch * EB), 0, next_row < batch ? in_len * EB : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *) (Z + (size_t) row * kM), 0, kM * 8, 0x00020000);
-        three_passes<INV>(v, plane, T, aux, wave_sgpr, false, false);      // v[p] = Z[t + 1024 br5(p)]
+        three_passes<INV>(v, plane, T, aux, wave_sgpr, wave_sgpr, false, false);      // v[p] = Z[t + 1024 br5(p)], t = reader_column
         if (INV) {
 #pragma unroll
             for (int p = 0; p < 32; ++p) v[p] = cf{v[p].x * kScale, v[p].y * kScale};

@@ -12,9 +12,10 @@
 //
 //   load    thread t = 32 j2 + j3 reads z[1024 j1 + t], j1 = 0..31       (coalesced 8 B / lane)
 //   pass 1  32-point DFT over j1 in registers, times W_1024^{j2 k1}
-//   xchg 1  transpose j2 <-> k1 through LDS (re plane, then im plane: 136 KiB each)
+//   xchg 1  transpose j2 <-> k1 through LDS: complex values, one class of register groups at a time through a 132 KiB
+//           buffer, pipelined behind the butterflies of the next group (see exchange())
 //   pass 2  32-point DFT over j2, times W_32768^{j3 (k1 + 32 k2)}
-//   xchg 2  transpose j3 <-> k2 through LDS; the reader picks the column k' = k1 + 32 k2 so
+//   xchg 2  transpose j3 <-> k2 the same way; the reader picks the column k' = k1 + 32 k2 so
 //           that lane l and lane 63-l of a wave hold columns k' and 1024-k'
 //   pass 3  32-point DFT over j3: Z[k' + 1024 k3]
 //   post    packed-real untangling (dsc_fft.h:199-225) needs Z[k] and Z[M-k]: the partner
@@ -49,9 +50,8 @@ __device__ __forceinline__ cf to_cf(f2 a) { return cf{a.x, a.y}; }
 __device__ __forceinline__ f2 to_f2(cf a) { return f2{a.x, a.y}; }
 
 constexpr int kM = 32768;            // complex points per row
-constexpr int kRowPitch = 34;        // floats per LDS row: 32 + 2 -> conflict-free b64 row reads
-constexpr int kPlaneFloats = 1024 * kRowPitch;
-constexpr int kLdsBytes = kPlaneFloats * 4 + 1024 * 8;      // exchange plane + twiddle table T
+constexpr int kPlaneFloats = 1024 * 34;                     // 136 KiB: the transposes' step buffer (132 KiB) and the store staging area (128 KiB + 16 bins)
+constexpr int kLdsBytes = kPlaneFloats * 4 + 1024 * 8;      // plane + twiddle table T
 constexpr int kTabEntries = 1024;
 
 // aux table layout (f2 entries): [0,1024) W_1024^m | [1024,2048) W_32768^m | [2048,3072) W_65536^m
@@ -84,6 +84,19 @@ __device__ __forceinline__ cf cmul(cf a, cf w) {
 }
 __device__ __forceinline__ cf cmul_conj(cf a, cf w) {     // a * conj(w)
     return cf{a.x * w.x + a.y * w.y, a.y * w.x - a.x * w.y};
+}
+
+// The same products with the contraction spelled out: the first product of each component rounded, the second fused — where
+// hipcc, left to -ffp-contract=fast, fuses the first of a difference.  The four outputs of the DIT dft32 that are sums only
+// (bins 0, 8, 16, 24) took this form in pass 2 while the transposes moved one float component at a time (the compiler kept
+// them as vector values); spelling it out keeps the results of rfft, irfft and the fused filter bit-identical to that version
+// (profiles/exchange_pipeline_64k.md, section 6).  It is a special case whose only purpose is that identity: dropping it is a
+// numeric change (last bits, the same error against float64) to be made on purpose and recorded, not a simplification — compare
+// the sha256 of `bench.py --dump-outputs` before and after.
+template<bool INV>
+__device__ __forceinline__ cf twiddle_mul_second_fused(cf a, cf w) {
+    if (INV) return cf{__builtin_fmaf(a.y, w.y, a.x * w.x), __builtin_fmaf(-a.x, w.y, a.y * w.x)};
+    return cf{__builtin_fmaf(-a.y, w.y, a.x * w.x), __builtin_fmaf(a.y, w.x, a.x * w.y)};
 }
 
 // d * W_M^K (forward) or d * conj(W_M^K) (INV), K < M/2, constants folded at compile time
@@ -132,6 +145,18 @@ __device__ __forceinline__ void dft32(cf (&v)[32]) {
     dif_stage<INV, 2>(v, std::make_integer_sequence<int, 16>{});
 }
 
+// The same graph cut after stage 2: the four quarters v[8 Q .. 8 Q + 7] are then independent 8-point transforms.
+template<bool INV>
+__device__ __forceinline__ void dft32_head(cf (&v)[32]) {
+    dif_stage<INV, 32>(v, std::make_integer_sequence<int, 1>{});
+    dif_stage<INV, 16>(v, std::make_integer_sequence<int, 2>{});
+}
+template<bool INV, int Q>
+__device__ __forceinline__ void dft32_quarter(cf (&v)[32]) {
+    dif_stage<INV, 8>(v, std::integer_sequence<int, Q>{});
+    dif_stage<INV, 4>(v, std::integer_sequence<int, 2 * Q, 2 * Q + 1>{});
+    dif_stage<INV, 2>(v, std::integer_sequence<int, 4 * Q, 4 * Q + 1, 4 * Q + 2, 4 * Q + 3>{});
+}
 
 #else
 // The same transform as the decimation-in-time graph with natural-order input and bit-reversed output: stage s (half distance
@@ -210,32 +235,24 @@ __device__ __forceinline__ void dft32(cf (&v)[32]) {
     dit_stage<INV, 4>(v, std::make_integer_sequence<int, 8>{});
     dit_stage<INV, 5>(v, std::make_integer_sequence<int, 16>{});
 }
+
+// The same graph cut after stage 2: the four quarters v[8 Q .. 8 Q + 7] are then independent 8-point transforms.
+template<bool INV>
+__device__ __forceinline__ void dft32_head(cf (&v)[32]) {
+    dit_stage<INV, 1>(v, std::make_integer_sequence<int, 1>{});
+    dit_stage<INV, 2>(v, std::make_integer_sequence<int, 2>{});
+}
+template<bool INV, int Q>
+__device__ __forceinline__ void dft32_quarter(cf (&v)[32]) {
+    dit_stage<INV, 3>(v, std::integer_sequence<int, Q>{});
+    dit_stage<INV, 4>(v, std::integer_sequence<int, 2 * Q, 2 * Q + 1>{});
+    dit_stage<INV, 5>(v, std::integer_sequence<int, 4 * Q, 4 * Q + 1, 4 * Q + 2, 4 * Q + 3>{});
+}
 #endif
 
 typedef unsigned int u2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u4 __attribute__((ext_vector_type(4)));
 typedef float f4 __attribute__((ext_vector_type(4)));
-
-// LDS transpose of one float plane: every thread writes 32 floats at wbase + slot * 1088
-// (slot = br5(p): register p of a DIF output holds logical index br5(p)) and reads back its
-// own row of 32 as 16 x b64.  Two base registers cover all 32 slots with 16-bit immediates.
-template<int COMP>
-__device__ __forceinline__ void plane_write(float *plane, int wbase, const cf (&v)[32]) {
-    // The second base is opaque: left to itself the compiler folds it back into the first, finds the offsets of slots 16..31
-    // beyond the 16-bit immediate and builds one address per write (16 v_add_u32 and 16 unpaired ds_write_b32 per plane).
-    // With two bases every slot is base + slot' * 4352 B, slot' < 16: all 32 writes pair into ds_write2st64_b32 (17 slot' <= 255);
-    // 0.837-0.842 -> 0.830-0.838 ms on the rfft kernel.
-    int wbase_hi = wbase + 16 * (32 * kRowPitch);
-    asm("" : "+v"(wbase_hi));
-    float *lo16 = plane + wbase;
-    float *hi16 = plane + wbase_hi;
-    // even registers hold slots 0..15, odd ones slots 16..31: one base at a time (writes through the other base, whose
-    // distance the compiler cannot see, would stand between the two halves of a pair)
-#pragma unroll
-    for (int p = 0; p < 32; p += 2) lo16[br5(p) * (32 * kRowPitch)] = COMP == 0 ? v[p].x : v[p].y;
-#pragma unroll
-    for (int p = 1; p < 32; p += 2) hi16[(br5(p) - 16) * (32 * kRowPitch)] = COMP == 0 ? v[p].x : v[p].y;
-}
 
 // One 8-byte LDS read that stays one ds_read_b64.  hipcc fuses neighbouring 8-byte reads of one base into ds_read2_b64,
 // which moves half as much per clock (tools/ldsbench.hip: 4.15 against 2.40 cycles per wave and 8 B/lane), and the row
@@ -253,19 +270,6 @@ __device__ __forceinline__ f2 lds_read_b64(const f2 *p) {
 #else
     return *p;
 #endif
-}
-
-// Row and column numbers are far below 2^24: their products with the pitch (here and in three_passes) take the full-rate
-// 24-bit multiply; v_mul_lo_u32 issues at a quarter of the rate.
-template<int COMP>
-__device__ __forceinline__ void plane_read(const float *plane, int row, cf (&v)[32]) {
-    const f2 *r = (const f2 *) (plane + __mul24(row, kRowPitch));
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-        const f2 t = lds_read_b64(r + m);
-        if (COMP == 0) { v[2 * m].x = t.x; v[2 * m + 1].x = t.y; }
-        else           { v[2 * m].y = t.x; v[2 * m + 1].y = t.y; }
-    }
 }
 
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e.
@@ -361,65 +365,165 @@ __device__ __forceinline__ void fill_twiddle_table(f2 *T, const f2 *aux) {
     __syncthreads();
 }
 
-// One LDS transpose = re plane, then im plane.  Barriers sit AFTER each read phase (not before
-// each write phase): a wave's LDS writes then overlap the tail of its own butterflies and
-// the other waves' arithmetic; the last one leaves the plane free for whoever writes next.
-__device__ __forceinline__ void exchange(float *plane, int wbase, int row, const cf (&src)[32], cf (&dst)[32]) {
-    plane_write<0>(plane, wbase, src);
+// ---- LDS transposes, pipelined behind the butterflies ------------------------------------------------------------------------
+// A transpose sends register p of a writer (bin k = br5(p) of its 32-point DFT) to the reader thread whose coordinate is k,
+// so the registers of one CLASS of bins deliver all 32 inputs to one class of reader threads and nothing to the others.  The
+// two classes are k mod 4 in {0, 3} and k mod 4 in {1, 2}: after stage 2 of dft32 the quarters v[8 Q .. 8 Q + 7] are independent
+// and hold the bins = {0, 2, 1, 3}[Q] mod 4, i.e. class 0 is quarters 0 and 3, class 1 quarters 1 and 2.  (Pairs a, 3 - a because
+// the mirrored lanes l and 63 - l of the forward kernel hold coordinates k and 31 - k: both land in one class.)  A transpose is
+// two steps through ONE buffer of 512 reader rows x 32 COMPLEX values (132 KiB, inside the old float plane):
+//
+//      finish class 0 (stages 3-5 of its quarters, twiddles) | barrier: buffer free | write class 0 | barrier
+//      class-0 readers issue their 32 reads;  EVERY wave finishes class 1 meanwhile             | barrier: reads drained
+//      write class 1 | barrier | class-1 readers read;  class-0 readers are already in their next DFT
+//
+// Reader classes are whole waves (but for one lane, see reader_of), two of each on every SIMD: while one wave of a SIMD waits for
+// the LDS another one has butterflies to run.  The plane-at-a-time form before this had every wave in the same LDS phase at
+// once: five of the twelve barrier intervals of a row held no vector arithmetic at all.
+constexpr int kCPitch = 33;          // complex per buffer row: ds_write_b64 (16-lane groups) and ds_read_b64 (32-lane groups) conflict free
+static_assert(512 * kCPitch * 8 <= kPlaneFloats * 4, "the step buffer lives inside the plane");
+
+__host__ __device__ constexpr int class_of(int k) { return (k ^ (k >> 1)) & 1; }                  // k mod 4: 0, 3 -> 0;  1, 2 -> 1
+__host__ __device__ constexpr int index_in_class(int k) { return ((k >> 2) << 1) | (k & 1); }     // 0 .. 15 within its class
+static_assert(class_of(br5(0)) == 0 && class_of(br5(7)) == 0 && class_of(br5(24)) == 0 && class_of(br5(31)) == 0 &&
+              class_of(br5(8)) == 1 && class_of(br5(23)) == 1, "class 0 = quarters 0 and 3 of a dft32 output");
+
+// Which (32-row block, lane) a thread READS in a transpose with natural-order readers, as row / column number
+// 32 k + (t & 31): the two class bits of k are the two high bits of the wave number, so that a class is made of whole waves —
+// waves 0-3 and 12-15 against 4-11 — and every SIMD (wave mod 4) holds two waves of each.
+__device__ __forceinline__ int reader_column(int t) {
+    const int a = t >> 5;
+    return (t & 31) | ((((a >> 3) | ((a & 7) << 2))) << 5);
+}
+// The same for the mirrored spectrum side (column_of): the wave that holds the columns of `wave` there.  Wave 0 stays wave 0.
+__device__ __forceinline__ int spectrum_wave(int wave_sgpr) { return (wave_sgpr >> 2) | ((wave_sgpr & 3) << 2); }
+
+// Quarter Q of a dft32 output to the step buffer of its class: register p (bin k = br5(p)) goes to row block index_in_class(k), at
+// wbase = (row within the block) * kCPitch + (column), in complex units.  Two bases cover the 16 blocks with 16-bit
+// immediates; the second is opaque so that the compiler does not fold it back and build one address per write.
+template<int Q>
+__device__ __forceinline__ void quarter_write(f2 *buf, int wbase, const cf (&v)[32]) {
+    int wbase_hi = wbase + 8 * (32 * kCPitch);
+    asm("" : "+v"(wbase_hi));
+    f2 *lo8 = buf + wbase;
+    f2 *hi8 = buf + wbase_hi;
+#pragma unroll
+    for (int p = 8 * Q; p < 8 * Q + 8; ++p)
+        if (index_in_class(br5(p)) < 8) lo8[index_in_class(br5(p)) * (32 * kCPitch)] = to_f2(v[p]);
+#pragma unroll
+    for (int p = 8 * Q; p < 8 * Q + 8; ++p)
+        if (index_in_class(br5(p)) >= 8) hi8[(index_in_class(br5(p)) - 8) * (32 * kCPitch)] = to_f2(v[p]);
+}
+
+// A reader's 32 inputs: one buffer row, single ds_read_b64 (see lds_read_b64).  Row numbers are far below 2^24: their
+// products with the pitch take the full-rate 24-bit multiply; v_mul_lo_u32 issues at a quarter of the rate.
+__device__ __forceinline__ void step_read(const f2 *buf, int row, cf (&dst)[32]) {
+    const f2 *r = buf + __mul24(row, kCPitch);
+#pragma unroll
+    for (int m = 0; m < 32; ++m) dst[m] = to_cf(lds_read_b64(r + m));
+}
+
+// The values of v[] exist here, in program order: left alone the compiler sinks the butterflies that only a later group needs
+// down to that group, across the barriers, and keeps their inputs alive instead (spills).
+__device__ __forceinline__ void pin(cf (&v)[32]) {
+#pragma unroll
+    for (int p = 0; p < 32; p += 8)
+        asm volatile("" : "+v"(v[p].x), "+v"(v[p].y), "+v"(v[p + 1].x), "+v"(v[p + 1].y), "+v"(v[p + 2].x), "+v"(v[p + 2].y), "+v"(v[p + 3].x),
+                     "+v"(v[p + 3].y), "+v"(v[p + 4].x), "+v"(v[p + 4].y), "+v"(v[p + 5].x), "+v"(v[p + 5].y), "+v"(v[p + 6].x), "+v"(v[p + 6].y),
+                     "+v"(v[p + 7].x), "+v"(v[p + 7].y));
+}
+
+// One transpose.  finish(std::integral_constant<int, Q>) completes quarter Q of src (the rest of its DFT and its twiddles);
+// rclass / rrow: the class this thread reads in and its row there (coordinate k: index_in_class(k) * 32 + row within block).
+// The barrier that frees the buffer after the class-1 reads is the first one of whatever writes the plane next.
+template<typename Finish>
+__device__ __forceinline__ void exchange(f2 *buf, int wbase, int rclass, int rrow, cf (&src)[32], cf (&dst)[32], Finish finish) {
+    pin(src);
+    lds_barrier();                                         // buffer free
+    finish(std::integral_constant<int, 0>{});
+    quarter_write<0>(buf, wbase, src);
+    finish(std::integral_constant<int, 3>{});
+    quarter_write<3>(buf, wbase, src);
     lds_barrier();
-    plane_read<0>(plane, row, dst);
+    cf r[32];                                              // fresh registers: whatever dst held before must not stay alive for the lanes that skip a read
+    if (rclass == 0) step_read(buf, rrow, r);
+    finish(std::integral_constant<int, 1>{});
+    lds_barrier();                                         // class-0 reads drained (one quarter's twiddles in flight at a time: the readers' 64 registers are live here)
+    quarter_write<1>(buf, wbase, src);
+    finish(std::integral_constant<int, 2>{});
+    quarter_write<2>(buf, wbase, src);
     lds_barrier();
-    plane_write<1>(plane, wbase, src);
-    lds_barrier();
-    plane_read<1>(plane, row, dst);
-    lds_barrier();
+    if (rclass != 0) step_read(buf, rrow, r);
+#pragma unroll
+    for (int m = 0; m < 32; ++m) dst[m] = r[m];
 }
 
 // Three passes of the 32768-point complex DFT (forward, or INV = conjugate twiddles).
-//   in : v[i] = element 1024 i + t of the input sequence, t = thread id, i = 0..31
-//        (forward: time samples z[j]; inverse: bins Z[k] — any thread may hold any column
-//         `col`, the exchange routes by column: pass `col` = the column this thread holds)
-//   out: v[p] = element col_out + 1024 br5(p) of the output sequence, where the caller picks
-//        which output column `col_out` this thread receives.
+//   in : v[i] = element 1024 i + col of the input sequence, i = 0..31; col = t, the thread id (forward: time samples z[j]),
+//        or with mirrored_in col = column_of(col_wave, lane) (inverse: bins Z[k]); the exchange routes by column
+//   out: v[p] = element col_out + 1024 br5(p) of the output sequence; col_out = reader_column(t), or with mirrored_out
+//        column_of(col_wave, lane).
+//   The buffer is the caller's again after a barrier (the class-1 readers of the second transpose may still be reading).
 struct no_hook { __device__ __forceinline__ void operator()() const {} };
 
 // `before_pass3` runs between the second exchange and the last 32-point DFT: from there to the end of the row only v[] (64
 // VGPRs) is live, which leaves room to request part of the NEXT row that early (irfft64k_kernel does).
 template<bool INV, typename Hook = no_hook>
-__device__ __forceinline__ void three_passes(cf (&v)[32], float *plane, const f2 *T, const f2 *aux, int wave_sgpr,
+__device__ __forceinline__ void three_passes(cf (&v)[32], float *plane, const f2 *T, const f2 *aux, int wave_sgpr, int col_wave,
                                              bool mirrored_in, bool mirrored_out, Hook before_pass3 = Hook{}) {
+    f2 *buf = (f2 *) plane;
+    // readers with natural-order coordinates: the class is a property of the wave (a scalar: the reads sit behind a branch)
+    const int wave_class = ((wave_sgpr >> 2) ^ (wave_sgpr >> 3)) & 1;
     // ---- pass 1 (over the slow index) and twiddle W_1024^{hi r1}, hi = col >> 5
-    dft32<INV>(v);
+    dft32_head<INV>(v);
     cf u[32];
     {
         const int t = thread_id(wave_sgpr);
-        const int col = mirrored_in ? column_of(t >> 6, t & 63) : t;
+        const int col = mirrored_in ? column_of(col_wave, t & 63) : t;
         const int hi = col >> 5;
         const f2 *th = T + hi;                            // T[r1][hi]: hi takes two (mirrored: three) values per wave, the reads broadcast
+        // exchange 1: (hi, lo)[r1] -> thread (r1, lo), registers [hi];  buffer row = (r1 within its class) * 32 + lo, col = hi
+        const int rc = reader_column(t);
+        exchange(buf, __mul24(col & 31, kCPitch) + hi, wave_class, (index_in_class(rc >> 5) << 5) | (rc & 31), v, u, [&](auto Q) {
+            constexpr int kQ = decltype(Q)::value;
+            dft32_quarter<INV, kQ>(v);
 #pragma unroll
-        for (int r1 = 1; r1 < 32; ++r1) {
-            const cf w = to_cf(th[32 * r1]);
-            v[br5(r1)] = INV ? cmul_conj(v[br5(r1)], w) : cmul(v[br5(r1)], w);
-        }
-        // exchange 1: (hi, lo)[r1] -> thread (r1, lo), registers [hi];  LDS row = r1*32 + lo, col = hi
-        exchange(plane, __mul24(col & 31, kRowPitch) + hi, t, v, u);
+            for (int p = 8 * kQ; p < 8 * kQ + 8; ++p) {
+                if (p == 0) continue;
+                const cf w = to_cf(th[32 * br5(p)]);
+                v[p] = INV ? cmul_conj(v[p], w) : cmul(v[p], w);
+            }
+        });
     }
     // ---- pass 2 (over the middle index) and twiddle W_32768^{lo r1} W_1024^{lo r2}
-    dft32<INV>(u);
+    dft32_head<INV>(u);
     {
         const int t = thread_id(wave_sgpr);
-        const int hi = t >> 5, lo = t & 31;              // (r1, lo)
+        const int rc = reader_column(t);
+        const int hi = rc >> 5, lo = rc & 31;            // (r1, lo)
         const cf tw2_base = to_cf(aux[kAuxW32768 + __mul24(hi, lo)]);
-        u[0] = INV ? cmul_conj(u[0], tw2_base) : cmul(u[0], tw2_base);
         const f2 *tl = T + lo;                            // T[r2][lo]: the lanes read consecutive entries
+        // exchange 2: (r1, lo)[r2] -> output column r1 + 32 r2, registers [lo];  buffer row = (r2 within its class) * 32 + r1
+        const int col_out = mirrored_out ? column_of(col_wave, t & 63) : rc;
+        const int k2 = col_out >> 5;
+        // mirrored: lanes l and 63 - l hold k2 and 31 - k2, one class — but for lane 63 (k2 = 32 - col_wave), which reads
+        // with the other class when col_wave is odd: a per-lane class there
+        const int rclass = mirrored_out ? class_of(k2) : wave_class;
+        exchange(buf, __mul24(hi, kCPitch) + lo, rclass, (index_in_class(k2) << 5) | (col_out & 31), u, v, [&](auto Q) {
+            constexpr int kQ = decltype(Q)::value;
+            dft32_quarter<INV, kQ>(u);
+#ifdef DSC_DFT32_DIF
+            constexpr bool kSumsOnly = false;
+#else
+            constexpr bool kSumsOnly = true;               // registers 0 .. 3: bins 0, 16, 8, 24 (see twiddle_mul_second_fused)
+#endif
 #pragma unroll
-        for (int r2 = 1; r2 < 32; ++r2) {
-            const cf w = cmul(tw2_base, to_cf(tl[32 * r2]));
-            u[br5(r2)] = INV ? cmul_conj(u[br5(r2)], w) : cmul(u[br5(r2)], w);
-        }
-        // exchange 2: (r1, lo)[r2] -> output column r1 + 32 r2, registers [lo];  LDS row = column
-        const int col_out = mirrored_out ? column_of(t >> 6, t & 63) : t;
-        exchange(plane, __mul24(hi, kRowPitch) + lo, col_out, u, v);
+            for (int p = 8 * kQ; p < 8 * kQ + 8; ++p) {
+                const cf w = p == 0 ? tw2_base : cmul(tw2_base, to_cf(tl[32 * br5(p)]));
+                if (kSumsOnly && p < 4) u[p] = twiddle_mul_second_fused<INV>(u[p], w);
+                else u[p] = INV ? cmul_conj(u[p], w) : cmul(u[p], w);
+            }
+        });
     }
     before_pass3();
     // ---- pass 3 (over the fast index)
@@ -482,7 +586,8 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
         const __amdgpu_buffer_rsrc_t rout =
             __builtin_amdgcn_make_buffer_rsrc((void *) (X + (size_t) row * (kM + 1)), 0, (kM + 1) * 8 * IO_ON, 0x00020000);
 
-        three_passes<false>(v, plane, T, aux, wave_sgpr, false, true);     // v[p] = Z[k' + 1024 br5(p)]
+        const int cw = spectrum_wave(wave_sgpr);          // this wave holds the spectrum columns column_of(cw, lane)
+        three_passes<false>(v, plane, T, aux, wave_sgpr, cw, false, true); // v[p] = Z[k' + 1024 br5(p)]
         // (Requesting part of the next row before pass 3, as irfft64k_kernel does, was tried here too: it needs pass 3's results
         // pinned — the compiler otherwise sinks the butterflies into the post-pass and the merged region takes all 128
         // registers — and then fits 4 loads, which measured 0.842-0.849 ms against 0.845-0.849 ms: nothing.)
@@ -492,11 +597,11 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
         // xk[k3] = X[k], xm[k3] = X[M-k], k = k' + 1024 k3.
         const int t4 = thread_id(wave_sgpr);
         const int lane = t4 & 63, wave = t4 >> 6;
-        const int kp = column_of(wave, lane);
-        const int partner_addr = partner_byte_addr(wave, lane);
+        const int kp = column_of(cw, lane);
+        const int partner_addr = partner_byte_addr(cw, lane);
         cf xk[16], xm[16];
         const cf zmid = v[br5(16)];                        // Z[M/2] in column 0
-        if (wave_sgpr == 0) {
+        if (cw == 0) {                                     // = wave 0
             // Column 0 (lane 0, its own partner) pairs row k3 with row 32 - k3 of ITSELF, not 31 - k3: shift its rows 17 .. 31
             // down by one (and row 0 into row 31) BEFORE the exchange, so that the general fetch below is right for it too and
             // the sent rows die with their ds_bpermute — fixing the fetched values up afterwards kept all 32 of them alive
@@ -530,6 +635,7 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
         f2 *stage = (f2 *) plane;
         const int skew = (int) ((((size_t) (X + (size_t) row * (kM + 1))) >> 3) & 15);     // bins past a line start
         // half 1: bins [0, 16384 - skew)
+        lds_barrier();                                     // the last readers of the second transpose have left the plane
 #pragma unroll
         for (int k3 = 0; k3 < 16; ++k3) stage[kp + 1024 * k3] = to_f2(xk[k3]);
         const cf xk15 = xk[15];
@@ -571,8 +677,7 @@ __global__ __launch_bounds__(1024) void rfft64k_kernel(const float *__restrict__
                 __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u2, stage[k - kStage2]), rout, k * 8, 0, kStream);
             }
             if (m & 1) __builtin_amdgcn_sched_barrier(0);
-        }
-        lds_barrier();                                     // plane free for the next row's exchange 1
+        }                                                  // (the next row's first transpose waits for these reads itself)
     }
 }
 
@@ -628,14 +733,17 @@ __device__ __forceinline__ void inverse_prepass_direct(cf (&v)[32], cf y_mid, co
 // whole lines, 16 B per lane; as soon as a half has left the registers the next row's loads are
 // issued into them (`issue_next(first_half)`), ahead of this row's stores.  Register p holds
 // row br5(p): even p = rows 0..15 = first half.  On return the even registers hold what
-// issue_next(true) loaded, the odd ones what issue_next(false) loaded.
+// issue_next(true) loaded, the odd ones what issue_next(false) loaded.  The thread's column t is reader_column(thread id),
+// as three_passes leaves it; the stores go by thread id.
 template<typename IssueNext>
 __device__ __forceinline__ void staged_time_store(cf (&v)[32], float *plane, __amdgpu_buffer_rsrc_t rout, int wave_sgpr,
                                                   IssueNext issue_next) {
     f2 *stage = (f2 *) plane;
     const int t4 = thread_id(wave_sgpr);
+    const int c4 = reader_column(t4);
+    lds_barrier();                                         // the last readers of the second transpose have left the plane
 #pragma unroll
-    for (int p = 0; p < 32; p += 2) stage[t4 + 1024 * br5(p)] = to_f2(v[p]);
+    for (int p = 0; p < 32; p += 2) stage[c4 + 1024 * br5(p)] = to_f2(v[p]);
     issue_next(true);
     lds_barrier();
 #pragma unroll
@@ -648,7 +756,7 @@ __device__ __forceinline__ void staged_time_store(cf (&v)[32], float *plane, __a
     }
     lds_barrier();
 #pragma unroll
-    for (int p = 1; p < 32; p += 2) stage[t4 + 1024 * (br5(p) - 16)] = to_f2(v[p]);
+    for (int p = 1; p < 32; p += 2) stage[c4 + 1024 * (br5(p) - 16)] = to_f2(v[p]);
     issue_next(false);
     lds_barrier();
 #pragma unroll
@@ -658,8 +766,7 @@ __device__ __forceinline__ void staged_time_store(cf (&v)[32], float *plane, __a
         const f4 q = f4{lo2.x, lo2.y, hi2.x, hi2.y};
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, q), rout, (kM / 2 + k) * 8, 0, kStream);
         if (m & 1) __builtin_amdgcn_sched_barrier(0);
-    }
-    lds_barrier();                                         // plane free for the next row's exchange 1
+    }                                                      // (the next row's first transpose waits for these reads itself)
 }
 
 // The pipelined loads land rows 0..15 in the even registers and rows 16..31 in the odd ones:
@@ -726,7 +833,7 @@ __global__ __launch_bounds__(1024) void irfft64k_kernel(const f2 *__restrict__ X
         // the staging area, the rest after the second half.  (kEarly = 0: everything in the tail, as the forward kernel does.)
         constexpr int kEarly = DSC_IRFFT_EARLY_PAIRS;
         cf early[kEarly > 0 ? 2 * kEarly : 1];
-        three_passes<true>(v, plane, T, aux, wave_sgpr, true, false, [&]() {      // v[p] = z[t + 1024 br5(p)]
+        three_passes<true>(v, plane, T, aux, wave_sgpr, wave_sgpr, true, false, [&]() {      // v[p] = z[t + 1024 br5(p)], t = reader_column
             if constexpr (kEarly > 0) {
                 const int t3 = thread_id(wave_sgpr);
                 const int c3 = column_of(t3 >> 6, t3 & 63);
@@ -816,13 +923,14 @@ __global__ __launch_bounds__(1024) void filter64k_kernel(const float *__restrict
             (void *) (x + (size_t) next_row * in_pitch), 0, next_row < batch ? in_len * 4 : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rout =
             __builtin_amdgcn_make_buffer_rsrc((void *) (y + (size_t) row * 65536), 0, 65536 * 4, 0x00020000);
-        three_passes<false>(v, plane, T, aux, wave_sgpr, false, true);     // v[p] = Z[c + 1024 br5(p)]
+        const int cw = spectrum_wave(wave_sgpr);          // this wave holds the spectrum columns column_of(cw, lane)
+        three_passes<false>(v, plane, T, aux, wave_sgpr, cw, false, true); // v[p] = Z[c + 1024 br5(p)]
 
         // ---- post-pass, multiply by H, pre-pass: all on the pair (k, M-k) held by this lane.
         // In place: register br5(r) holds row r of the column before (Z) and after (Z'/M).
         {
             const int t1 = thread_id(wave_sgpr);
-            const int lane = t1 & 63, wave = t1 >> 6;
+            const int lane = t1 & 63, wave = cw;
             const int c = column_of(wave, lane);
             const int partner_addr = partner_byte_addr(wave, lane);
             const cf wc = to_cf(aux[kAuxW65536 + c]);
@@ -889,7 +997,7 @@ __global__ __launch_bounds__(1024) void filter64k_kernel(const float *__restrict
         // the next row's first kEarlyX loads are requested before the inverse transform's last pass (see irfft64k_kernel)
         constexpr int kEarlyX = DSC_FILTER_EARLY_LOADS;
         cf early[kEarlyX > 0 ? kEarlyX : 1];
-        three_passes<true>(z, plane, T, aux, wave_sgpr, true, false, [&]() {      // z[p] = y[2(t + 1024 br5(p)) .. +1]
+        three_passes<true>(z, plane, T, aux, wave_sgpr, cw, true, false, [&]() {  // z[p] = y[2(t + 1024 br5(p)) .. +1], t = reader_column
             if constexpr (kEarlyX > 0) {
                 const int off = thread_id(wave_sgpr) * 8;
 #pragma unroll

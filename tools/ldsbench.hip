@@ -1,6 +1,6 @@
 // tools/ldsbench.hip — LDS read forms of the 64k kernels on gfx950 (diagnostic): one 1024-thread workgroup per CU
 // (4 waves per SIMD), the exchange plane's 136-byte row pitch, the 8 KiB twiddle table behind it.
-//   row16xb64      every lane reads its own plane row as 16 x ds_read_b64            (what plane_read asks for)
+//   row16xb64      every lane reads its own plane row as 16 x ds_read_b64            (what the plane-at-a-time transposes read; the pipelined ones read 32 x ds_read_b64 at a 264-byte pitch, not covered here)
 //   row8xread2     the same 128 bytes as 8 x ds_read2_b64                            (what the compiler merges it into)
 //   tab_product    31 x ds_read_b64 of T[r][lo], lanes on consecutive 8-byte entries (product-indexed table)
 //   tab_lo_r2      31 x ds_read_b64 of w1024[lo * r2]                                (stride 2 r2 dwords: gcd(r2, 32)-way)
