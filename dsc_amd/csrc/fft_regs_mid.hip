@@ -949,34 +949,6 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
     }
 }
 
-template<typename R, int B, bool TWO>
-void launch_filter(const void *s, const void *H, void *y, long long n_lines, const void *tw_full, const void *tw_real, int in_pitch_b,
-                   int in_len_b, hipStream_t stream) {
-    using cfg = mid_cfg<R, B, TWO, 1>;
-    constexpr size_t lds = mid_lds_bytes<R, B, TWO, 1>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_filter_kernel<R, B, TWO>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
-    DSC_LAUNCH((fft_mid_filter_kernel<R, B, TWO>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, (const R *) s,
-                       (const cpx<R> *) H, (cpx<R> *) y, n_lines, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, in_pitch_b, in_len_b);
-}
-
-template<typename R>
-void launch_filter_len(int L, const void *s, const void *H, void *y, long long n_lines, const void *tw_full, const void *tw_real,
-                       int pb, int lb, hipStream_t stream) {
-    switch (L) {
-        case 256:   launch_filter<R, 8, true>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 512:   launch_filter<R, 16, true>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 1024:  launch_filter<R, 32, true>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 2048:  launch_filter<R, 2, false>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 4096:  launch_filter<R, 4, false>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 8192:  launch_filter<R, 8, false>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        default:    launch_filter<R, 16, false>(s, H, y, n_lines, tw_full, tw_real, pb, lb, stream); break;
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
 // Complex lengths 32 .. 256 (B = 1, 2, 4, 8 threads per line, real lengths 64 .. 512).  Lines this short cannot be read
 // coalesced in the "thread t owns elements B j1 + t" pattern, so the group's contiguous block of lines is copied to LDS
@@ -1153,49 +1125,59 @@ __global__ __launch_bounds__((small_cfg<R, MODE>::NT)) void fft_small_kernel(con
     }
 }
 
-template<typename R, int B, int MODE, bool INV, bool PAD>
-void launch_small_pad(const void *in, void *out, long long n_lines, const void *tw_full, const void *tw_real, double scale, int in_pitch, int in_len,
-                      hipStream_t stream) {
-    constexpr int G = small_cfg<R, MODE>::NT / B;
-    constexpr size_t lds = small_lds_bytes<R, B, MODE>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_small_kernel<R, B, MODE, INV, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + G - 1) / G;
-    DSC_LAUNCH((fft_small_kernel<R, B, MODE, INV, PAD>), dim3((unsigned) groups), dim3(small_cfg<R, MODE>::NT), lds, stream, in, out, n_lines,
-                       (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) scale, in_pitch, in_len);
-}
-// in_pitch < 0: full contiguous lines
-template<typename R, int B, int MODE, bool INV>
-void launch_small_one(const void *in, void *out, long long n_lines, const void *tw_full, const void *tw_real, double scale, long long in_pitch, int in_len,
-                      hipStream_t stream) {
-    if (in_pitch < 0) launch_small_pad<R, B, MODE, INV, false>(in, out, n_lines, tw_full, tw_real, scale, 0, 0, stream);
-    else              launch_small_pad<R, B, MODE, INV, true>(in, out, n_lines, tw_full, tw_real, scale, (int) in_pitch, in_len, stream);
+// ------------------------------------------------------------------------------------------------
+// Host side: from the run-time (precision, length, mode, direction) to the instantiation.  Each with_... hands its choice to a generic
+// callable as compile-time constants; a length without a kernel ends the process.
+template<int V> using int_c = std::integral_constant<int, V>;
+template<bool V> using bool_c = std::integral_constant<bool, V>;
+
+[[noreturn]] void no_kernel(const char *what, int L) {
+    fprintf(stderr, "fft_regs_mid.hip: no %s kernel for complex length %d\n", what, L);
+    exit(EXIT_FAILURE);
 }
 
-template<typename R, int B>
-void launch_small(const void *in, void *out, long long n_lines, dsc_fft_mode mode, bool inverse, const void *tw_full, const void *tw_real,
-                  double scale, long long in_pitch, int in_len, hipStream_t stream) {
-    if (mode == DSC_MODE_R2C_PACKED)      launch_small_one<R, B, DSC_MODE_R2C_PACKED, false>(in, out, n_lines, tw_full, tw_real, scale, in_pitch, in_len, stream);
-    else if (mode == DSC_MODE_C2R_PACKED) launch_small_one<R, B, DSC_MODE_C2R_PACKED, true>(in, out, n_lines, tw_full, tw_real, scale, in_pitch, in_len, stream);
-    else if (mode == DSC_MODE_R2C_CAST && !inverse) launch_small_one<R, B, DSC_MODE_R2C_CAST, false>(in, out, n_lines, tw_full, tw_real, scale, in_pitch, in_len, stream);
-    else if (mode == DSC_MODE_R2C_CAST)   launch_small_one<R, B, DSC_MODE_R2C_CAST, true>(in, out, n_lines, tw_full, tw_real, scale, in_pitch, in_len, stream);
-    else if (inverse)                     launch_small_one<R, B, DSC_MODE_C2C, true>(in, out, n_lines, tw_full, tw_real, scale, in_pitch, in_len, stream);
-    else                                  launch_small_one<R, B, DSC_MODE_C2C, false>(in, out, n_lines, tw_full, tw_real, scale, in_pitch, in_len, stream);
+template<typename F> void with_real(bool single_precision, F f) { if (single_precision) f(float{}); else f(double{}); }
+template<typename F> void with_bool(bool b, F f) { if (b) f(bool_c<true>{}); else f(bool_c<false>{}); }
+
+// (mode, inverse) -> (MODE, INV): the packed-real modes have one direction each
+template<typename F> void with_mode(dsc_fft_mode mode, bool inverse, F f) {
+    switch (mode) {
+        case DSC_MODE_R2C_PACKED: return f(int_c<DSC_MODE_R2C_PACKED>{}, bool_c<false>{});
+        case DSC_MODE_C2R_PACKED: return f(int_c<DSC_MODE_C2R_PACKED>{}, bool_c<true>{});
+        case DSC_MODE_R2C_CAST:   return with_bool(inverse, [&](auto inv) { f(int_c<DSC_MODE_R2C_CAST>{}, inv); });
+        case DSC_MODE_C2C:        return with_bool(inverse, [&](auto inv) { f(int_c<DSC_MODE_C2C>{}, inv); });
+    }
 }
 
-template<typename R, int B, bool TWO, int MODE, bool INV, bool PAD>
-void launch_pad(const void *in, void *out, long long n_lines, const void *tw_full, const void *tw_real, double scale, int in_pitch_b,
-                int in_len_b, hipStream_t stream) {
-    using cfg = mid_cfg<R, B, TWO>;
-    constexpr size_t lds = mid_lds_bytes<R, B, TWO>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_kernel<R, B, TWO, MODE, INV, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+// complex length -> (B, TWO) of fft_mid_kernel and fft_mid_filter_kernel (mid_cfg::L)
+template<typename F> void with_mid_len(int L, F f) {
+    switch (L) {
+        case 256:   return f(int_c<8>{}, bool_c<true>{});
+        case 512:   return f(int_c<16>{}, bool_c<true>{});
+        case 1024:  return f(int_c<32>{}, bool_c<true>{});
+        case 2048:  return f(int_c<2>{}, bool_c<false>{});
+        case 4096:  return f(int_c<4>{}, bool_c<false>{});
+        case 8192:  return f(int_c<8>{}, bool_c<false>{});
+        case 16384: return f(int_c<16>{}, bool_c<false>{});
+        default:    no_kernel("direct-load", L);
     }
-    long long groups = (n_lines + cfg::G - 1) / cfg::G;
-    if (cfg::PIPE) {                                        // persistent: one workgroup per CU walks the lines
+}
+
+// complex length -> B of fft_small_kernel (L = 32 B)
+template<typename F> void with_small_len(int L, F f) {
+    switch (L) {
+        case 32:  return f(int_c<1>{});
+        case 64:  return f(int_c<2>{});
+        case 128: return f(int_c<4>{});
+        case 256: return f(int_c<8>{});
+        default:  no_kernel("LDS-staged", L);
+    }
+}
+
+// workgroups of G lines each; a persistent kernel (mid_cfg::PIPE) gets one per CU at the most and walks the lines
+unsigned groups_of(long long n_lines, int G, bool persistent = false) {
+    long long groups = (n_lines + G - 1) / G;
+    if (persistent) {
         static int cus[64];
         int dev = 0;
         DSC_KERNEL_CHECK(hipGetDevice(&dev));
@@ -1203,27 +1185,52 @@ void launch_pad(const void *in, void *out, long long n_lines, const void *tw_ful
         if (cus[dev] == 0) DSC_KERNEL_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
         if (groups > cus[dev]) groups = cus[dev];
     }
-    DSC_LAUNCH((fft_mid_kernel<R, B, TWO, MODE, INV, PAD>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, (const cpx<R> *) in,
-                       (cpx<R> *) out, n_lines, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) scale, in_pitch_b, in_len_b);
+    return (unsigned) groups;
 }
 
-// in_pitch_b < 0: full contiguous lines (the fast instantiation)
-template<typename R, int B, bool TWO, int MODE, bool INV>
-void launch_one(const void *in, void *out, long long n_lines, const void *tw_full, const void *tw_real, double scale, int in_pitch_b,
-                int in_len_b, hipStream_t stream) {
-    if (in_pitch_b < 0) launch_pad<R, B, TWO, MODE, INV, false>(in, out, n_lines, tw_full, tw_real, scale, 0, 0, stream);
-    else                launch_pad<R, B, TWO, MODE, INV, true>(in, out, n_lines, tw_full, tw_real, scale, in_pitch_b, in_len_b, stream);
+// The transform kernels at complex length L: fft_small_kernel for 32 .. 256, else fft_mid_kernel; in_pitch_b / in_len_b in bytes (PAD
+// only).  SRC: none, or the stft_frames of dsc_stft.
+template<typename R, int MODE, bool INV, bool PAD, typename... SRC>
+void launch_lines_len(int L, const void *in, void *out, long long n_lines, const void *tw_full, const void *tw_real, double scale, int in_pitch_b,
+                      int in_len_b, hipStream_t stream, SRC... src) {
+    using C = cpx<R>;
+    constexpr bool FRAMES = sizeof...(SRC) != 0;
+    const auto mid = [&](auto b, auto two) {
+        constexpr int B = decltype(b)::value;
+        constexpr bool TWO = decltype(two)::value;
+        using cfg = mid_cfg<R, B, TWO>;
+        if constexpr (FRAMES && cfg::L == 256) no_kernel("direct-load stft", L);      // frames of 256 points: the LDS-staged kernel only
+        else dsc_launch_dyn_lds<fft_mid_kernel<R, B, TWO, MODE, INV, PAD, SRC...>>(
+                 groups_of(n_lines, cfg::G, cfg::PIPE && !FRAMES), cfg::NT, mid_lds_bytes<R, B, TWO>(), stream, (const C *) in, (C *) out, n_lines,
+                 (const C *) tw_full, (const C *) tw_real, (R) scale, in_pitch_b, in_len_b, src...);
+    };
+    if (dsc_fft_regs_small_supports(L)) {
+        with_small_len(L, [&](auto b) {
+            constexpr int B = decltype(b)::value, NT = small_cfg<R, MODE>::NT;
+            dsc_launch_dyn_lds<fft_small_kernel<R, B, MODE, INV, PAD, SRC...>>(groups_of(n_lines, NT / B), NT, small_lds_bytes<R, B, MODE>(), stream, in, out,
+                                                                               n_lines, (const C *) tw_full, (const C *) tw_real, (R) scale, in_pitch_b,
+                                                                               in_len_b, src...);
+        });
+    } else if (L == 32768) {                                                    // the one special length: f32 complex data only
+        if constexpr (sizeof(R) == 4 && MODE == DSC_MODE_C2C && !FRAMES) mid(int_c<32>{}, bool_c<false>{});
+        else no_kernel("direct-load", L);
+    } else {
+        with_mid_len(L, mid);
+    }
 }
 
-template<typename R, int B, bool TWO>
-void launch_b(const void *in, void *out, long long n_lines, dsc_fft_mode mode, bool inverse, const void *tw_full, const void *tw_real,
-              double scale, int pb, int lb, hipStream_t stream) {
-    if (mode == DSC_MODE_R2C_PACKED)      launch_one<R, B, TWO, DSC_MODE_R2C_PACKED, false>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-    else if (mode == DSC_MODE_C2R_PACKED) launch_one<R, B, TWO, DSC_MODE_C2R_PACKED, true>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-    else if (mode == DSC_MODE_R2C_CAST && !inverse) launch_one<R, B, TWO, DSC_MODE_R2C_CAST, false>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-    else if (mode == DSC_MODE_R2C_CAST)   launch_one<R, B, TWO, DSC_MODE_R2C_CAST, true>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-    else if (inverse)                     launch_one<R, B, TWO, DSC_MODE_C2C, true>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-    else                                  launch_one<R, B, TWO, DSC_MODE_C2C, false>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
+// fft_mid_filter_kernel at complex length L with its source pack: none (filter), conv_frames or hilbert_rows
+template<typename R, typename... SRC>
+void launch_filter_len(int L, const void *s, const void *H, void *y, long long n_lines, const void *tw_full, const void *tw_real, int in_pitch_b,
+                       int in_len_b, hipStream_t stream, SRC... src) {
+    with_mid_len(L, [&](auto b, auto two) {
+        constexpr int B = decltype(b)::value;
+        constexpr bool TWO = decltype(two)::value;
+        using cfg = mid_cfg<R, B, TWO, 1>;
+        dsc_launch_dyn_lds<fft_mid_filter_kernel<R, B, TWO, SRC...>>(groups_of(n_lines, cfg::G), cfg::NT, mid_lds_bytes<R, B, TWO, 1>(), stream,
+                                                                     (const R *) s, (const cpx<R> *) H, (cpx<R> *) y, n_lines,
+                                                                     (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, in_pitch_b, in_len_b, src...);
+    });
 }
 
 }  // namespace
@@ -1236,52 +1243,18 @@ bool dsc_fft_regs_mid_supports(int L, dsc_fft_mode mode, bool single_precision) 
     return L == 256 || L == 512 || L == 1024 || L == 2048 || L == 4096 || L == 8192 || L == 16384;
 }
 
-template<typename R>
-static void launch_len(const void *in, void *out, long long n_lines, int L, dsc_fft_mode mode, bool inverse, const void *tw_full,
-                       const void *tw_real, double scale, int pb, int lb, hipStream_t stream) {
-    switch (L) {
-        case 256:   launch_b<R, 8, true>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-        case 512:   launch_b<R, 16, true>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-        case 1024:  launch_b<R, 32, true>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-        case 2048:  launch_b<R, 2, false>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-        case 4096:  launch_b<R, 4, false>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-        case 8192:  launch_b<R, 8, false>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-        default:    launch_b<R, 16, false>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, pb, lb, stream); break;
-    }
-}
-
 // in_pitch / in_len: input line pitch and valid length in INPUT ELEMENTS (reals for R2C_PACKED / R2C_CAST, complex otherwise);
-// in_pitch < 0 = full contiguous lines.
+// in_pitch < 0 = full contiguous lines (the fast instantiation).
 void dsc_launch_fft_regs_mid(const void *in, void *out, long long n_lines, int L, dsc_fft_mode mode, bool inverse, bool single_precision,
                              const void *tw_full, const void *tw_real, double scale, long long in_pitch, int in_len, hipStream_t stream) {
     if (n_lines <= 0) return;
-    if (dsc_fft_regs_small_supports(L)) {                                   // 32 .. 256 points: the LDS-staged kernel
-        const int eb = (single_precision ? 4 : 8) * ((mode == DSC_MODE_R2C_PACKED || mode == DSC_MODE_R2C_CAST) ? 1 : 2);
-        if (in_pitch >= 0) { in_pitch *= eb; in_len *= eb; }                  // the kernel counts bytes
-        if (single_precision) {
-            if (L == 32)       launch_small<float, 1>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-            else if (L == 64)  launch_small<float, 2>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-            else if (L == 128) launch_small<float, 4>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-            else               launch_small<float, 8>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-        } else {
-            if (L == 32)       launch_small<double, 1>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-            else if (L == 64)  launch_small<double, 2>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-            else if (L == 128) launch_small<double, 4>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-            else               launch_small<double, 8>(in, out, n_lines, mode, inverse, tw_full, tw_real, scale, in_pitch, in_len, stream);
-        }
-        return;
-    }
-    const int real_b = single_precision ? 4 : 8;
-    const int elem_b = (mode == DSC_MODE_R2C_PACKED || mode == DSC_MODE_R2C_CAST) ? real_b : 2 * real_b;
-    const int pb = in_pitch < 0 ? -1 : (int) (in_pitch * elem_b), lb = in_pitch < 0 ? 0 : in_len * elem_b;
-    if (!single_precision) {
-        launch_len<double>(in, out, n_lines, L, mode, inverse, tw_full, tw_real, scale, pb, lb, stream);
-    } else if (L == 32768) {
-        if (inverse) launch_one<float, 32, false, DSC_MODE_C2C, true>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-        else         launch_one<float, 32, false, DSC_MODE_C2C, false>(in, out, n_lines, tw_full, tw_real, scale, pb, lb, stream);
-    } else {
-        launch_len<float>(in, out, n_lines, L, mode, inverse, tw_full, tw_real, scale, pb, lb, stream);
-    }
+    const int eb = (single_precision ? 4 : 8) * ((mode == DSC_MODE_R2C_PACKED || mode == DSC_MODE_R2C_CAST) ? 1 : 2);
+    const bool padded = in_pitch >= 0;
+    const int pb = padded ? (int) (in_pitch * eb) : 0, lb = padded ? in_len * eb : 0;      // the kernels count bytes
+    with_real(single_precision, [&](auto real) { with_mode(mode, inverse, [&](auto m, auto inv) { with_bool(padded, [&](auto pad) {
+        launch_lines_len<decltype(real), decltype(m)::value, decltype(inv)::value, decltype(pad)::value>(L, in, out, n_lines, tw_full, tw_real, scale, pb,
+                                                                                                         lb, stream);
+    }); }); });
 }
 
 // y = irfft(rfft(s, 2L) * H) fused, L = 256 .. 16384: s = [n_lines][in_pitch] reals of which in_len <= 2L are used, H = [L + 1]
@@ -1289,56 +1262,12 @@ void dsc_launch_fft_regs_mid(const void *in, void *out, long long n_lines, int L
 void dsc_launch_filter_regs_mid(const void *s, const void *H, void *y, long long n_lines, int L, bool single_precision, const void *tw_full,
                                 const void *tw_real, long long in_pitch, int in_len, hipStream_t stream) {
     if (n_lines <= 0) return;
-    const int rb = single_precision ? 4 : 8;
-    if (single_precision) launch_filter_len<float>(L, s, H, y, n_lines, tw_full, tw_real, (int) (in_pitch * rb), in_len * rb, stream);
-    else                  launch_filter_len<double>(L, s, H, y, n_lines, tw_full, tw_real, (int) (in_pitch * rb), in_len * rb, stream);
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        constexpr int RB = sizeof(R);
+        launch_filter_len<R>(L, s, H, y, n_lines, tw_full, tw_real, (int) (in_pitch * RB), in_len * RB, stream);
+    });
 }
-
-namespace {
-
-template<typename R, int B, bool TWO>
-void launch_stft_mid(void *out, long long n_lines, const void *tw_full, const void *tw_real, const stft_frames<R> &fr, hipStream_t stream) {
-    using cfg = mid_cfg<R, B, TWO>;
-    constexpr size_t lds = mid_lds_bytes<R, B, TWO>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_kernel<R, B, TWO, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
-    DSC_LAUNCH((fft_mid_kernel<R, B, TWO, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, nullptr, (cpx<R> *) out, n_lines,
-               (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) 1, 0, 0, fr);
-}
-
-template<typename R, int B>
-void launch_stft_small(void *out, long long n_lines, const void *tw_full, const void *tw_real, const stft_frames<R> &fr, hipStream_t stream) {
-    constexpr int NT = small_cfg<R, DSC_MODE_R2C_PACKED>::NT, G = NT / B;
-    constexpr size_t lds = small_lds_bytes<R, B, DSC_MODE_R2C_PACKED>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_small_kernel<R, B, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + G - 1) / G;
-    DSC_LAUNCH((fft_small_kernel<R, B, DSC_MODE_R2C_PACKED, false, false, stft_frames<R>>), dim3((unsigned) groups), dim3(NT), lds, stream, nullptr, out, n_lines, (const cpx<R> *) tw_full,
-               (const cpx<R> *) tw_real, (R) 1, 0, 0, fr);
-}
-
-template<typename R>
-void launch_stft_len(int L, void *out, long long n_lines, const void *tw_full, const void *tw_real, const stft_frames<R> &fr, hipStream_t stream) {
-    switch (L) {
-        case 32:    launch_stft_small<R, 1>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 64:    launch_stft_small<R, 2>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 128:   launch_stft_small<R, 4>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 256:   launch_stft_small<R, 8>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 512:   launch_stft_mid<R, 16, true>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 1024:  launch_stft_mid<R, 32, true>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 2048:  launch_stft_mid<R, 2, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 4096:  launch_stft_mid<R, 4, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        case 8192:  launch_stft_mid<R, 8, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
-        default:    launch_stft_mid<R, 16, false>(out, n_lines, tw_full, tw_real, fr, stream); break;
-    }
-}
-
-}  // namespace
 
 bool dsc_stft_regs_supports(int n_fft) { return n_fft >= 64 && n_fft <= 32768 && (n_fft & (n_fft - 1)) == 0; }
 
@@ -1347,71 +1276,12 @@ bool dsc_stft_regs_supports(int n_fft) { return n_fft >= 64 && n_fft <= 32768 &&
 void dsc_launch_stft_regs(const void *x, const void *w, void *out, long long n_lines, int n_fft, int T, int n_frames, int hop, int pad,
                           bool reflect, bool single_precision, int x_bytes, const void *tw_full, const void *tw_real, hipStream_t stream) {
     if (n_lines <= 0) return;
-    if (single_precision) {
-        const stft_frames<float> fr{(const float *) x, (const float *) w, x_bytes, T, n_frames, hop, pad, reflect ? 1 : 0};
-        launch_stft_len<float>(n_fft / 2, out, n_lines, tw_full, tw_real, fr, stream);
-    } else {
-        const stft_frames<double> fr{(const double *) x, (const double *) w, x_bytes, T, n_frames, hop, pad, reflect ? 1 : 0};
-        launch_stft_len<double>(n_fft / 2, out, n_lines, tw_full, tw_real, fr, stream);
-    }
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        const stft_frames<R> fr{(const R *) x, (const R *) w, x_bytes, T, n_frames, hop, pad, reflect ? 1 : 0};
+        launch_lines_len<R, DSC_MODE_R2C_PACKED, false, false>(n_fft / 2, nullptr, out, n_lines, tw_full, tw_real, 1.0, 0, 0, stream, fr);
+    });
 }
-
-namespace {
-
-template<typename R, int B, bool TWO>
-void launch_conv(const void *H, long long n_lines, const void *tw_full, const void *tw_real, const conv_frames<R> &fr, hipStream_t stream) {
-    using cfg = mid_cfg<R, B, TWO, 1>;
-    constexpr size_t lds = mid_lds_bytes<R, B, TWO, 1>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_filter_kernel<R, B, TWO, conv_frames<R>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
-    DSC_LAUNCH((fft_mid_filter_kernel<R, B, TWO, conv_frames<R>>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, nullptr,
-               (const cpx<R> *) H, nullptr, n_lines, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, 0, 0, fr);
-}
-
-template<typename R>
-void launch_conv_len(int L, const void *H, long long n_lines, const void *tw_full, const void *tw_real, const conv_frames<R> &fr, hipStream_t stream) {
-    switch (L) {
-        case 256:   launch_conv<R, 8, true>(H, n_lines, tw_full, tw_real, fr, stream); break;
-        case 512:   launch_conv<R, 16, true>(H, n_lines, tw_full, tw_real, fr, stream); break;
-        case 1024:  launch_conv<R, 32, true>(H, n_lines, tw_full, tw_real, fr, stream); break;
-        case 2048:  launch_conv<R, 2, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
-        case 4096:  launch_conv<R, 4, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
-        case 8192:  launch_conv<R, 8, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
-        default:    launch_conv<R, 16, false>(H, n_lines, tw_full, tw_real, fr, stream); break;
-    }
-}
-
-template<typename R, int B, bool TWO, bool ENV>
-void launch_hilbert(const void *x, void *out, long long n_lines, const void *tw_full, const void *tw_real, int in_pitch_b, int in_len_b,
-                    hipStream_t stream) {
-    using cfg = mid_cfg<R, B, TWO, 1>;
-    constexpr size_t lds = mid_lds_bytes<R, B, TWO, 1>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_mid_filter_kernel<R, B, TWO, hilbert_rows<R, ENV>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + cfg::G - 1) / cfg::G;
-    DSC_LAUNCH((fft_mid_filter_kernel<R, B, TWO, hilbert_rows<R, ENV>>), dim3((unsigned) groups), dim3(cfg::NT), lds, stream, (const R *) x, nullptr,
-               nullptr, n_lines, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, in_pitch_b, in_len_b, hilbert_rows<R, ENV>{out});
-}
-
-template<typename R, bool ENV>
-void launch_hilbert_len(int L, const void *x, void *out, long long n_lines, const void *tw_full, const void *tw_real, int pb, int lb, hipStream_t stream) {
-    switch (L) {
-        case 256:   launch_hilbert<R, 8, true, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 512:   launch_hilbert<R, 16, true, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 1024:  launch_hilbert<R, 32, true, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 2048:  launch_hilbert<R, 2, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 4096:  launch_hilbert<R, 4, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        case 8192:  launch_hilbert<R, 8, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-        default:    launch_hilbert<R, 16, false, ENV>(x, out, n_lines, tw_full, tw_real, pb, lb, stream); break;
-    }
-}
-
-}  // namespace
 
 bool dsc_hilbert_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n - 1)) == 0; }
 
@@ -1419,14 +1289,12 @@ bool dsc_hilbert_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n
 void dsc_launch_hilbert_regs(const void *x, void *out, long long n_lines, int n, bool envelope, bool single_precision, const void *tw_full,
                              const void *tw_real, long long in_pitch, int in_len, hipStream_t stream) {
     if (n_lines <= 0) return;
-    const int rb = single_precision ? 4 : 8, pb = (int) (in_pitch * rb), lb = in_len * rb;
-    if (single_precision) {
-        if (envelope) launch_hilbert_len<float, true>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
-        else          launch_hilbert_len<float, false>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
-    } else {
-        if (envelope) launch_hilbert_len<double, true>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
-        else          launch_hilbert_len<double, false>(n / 2, x, out, n_lines, tw_full, tw_real, pb, lb, stream);
-    }
+    with_real(single_precision, [&](auto real) { with_bool(envelope, [&](auto env) {
+        using R = decltype(real);
+        constexpr int RB = sizeof(R);
+        launch_filter_len<R>(n / 2, x, nullptr, nullptr, n_lines, tw_full, tw_real, (int) (in_pitch * RB), in_len * RB, stream,
+                             hilbert_rows<R, decltype(env)::value>{out});
+    }); });
 }
 
 bool dsc_conv_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n - 1)) == 0; }
@@ -1435,11 +1303,9 @@ bool dsc_conv_regs_supports(int n) { return n >= 512 && n <= 32768 && (n & (n - 
 void dsc_launch_conv_regs(const void *x, const void *H, void *y, long long n_lines, int n, int T, int n_blocks, int hop, int pad, int D, int T_out,
                           bool single_precision, int x_bytes, int y_bytes, const void *tw_full, const void *tw_real, hipStream_t stream) {
     if (n_lines <= 0) return;
-    if (single_precision) {
-        const conv_frames<float> fr{{(const float *) x, nullptr, x_bytes, T, n_blocks, hop, pad, 0}, (float *) y, y_bytes, D, T_out};
-        launch_conv_len<float>(n / 2, H, n_lines, tw_full, tw_real, fr, stream);
-    } else {
-        const conv_frames<double> fr{{(const double *) x, nullptr, x_bytes, T, n_blocks, hop, pad, 0}, (double *) y, y_bytes, D, T_out};
-        launch_conv_len<double>(n / 2, H, n_lines, tw_full, tw_real, fr, stream);
-    }
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        const conv_frames<R> fr{{(const R *) x, nullptr, x_bytes, T, n_blocks, hop, pad, 0}, (R *) y, y_bytes, D, T_out};
+        launch_filter_len<R>(n / 2, nullptr, H, nullptr, n_lines, tw_full, tw_real, 0, 0, stream, fr);
+    });
 }

@@ -1,8 +1,8 @@
-"""GPU tests of dsc_rfft / dsc_irfft / dsc_fft / dsc_ifft on every kernel route of fft_driver.cpp run_job, every line against the
+"""GPU tests of dsc_rfft / dsc_irfft / dsc_fft / dsc_ifft on every kernel route of fft_driver.cpp (its `routes` table), every line against the
 long-double reference of tests/test_fft_ref.py under the per-line bound an FFT obeys:
     per line  ||y - ref||_2 <= tau ||ref||_2,   |y_k - ref_k| <= tau (8 ||ref||_2 / sqrt(len) + |ref_k| + max |ref| / 8)
 (cols_4step_real: ||ref|| and max |ref| of the pair of neighbouring columns it transforms as one complex column)
-Every case asserts dsc.last_fft_path() (expect() below restates run_job's routing for a roomy context), checks that the input is left
+Every case asserts dsc.last_fft_path() (expect() below restates the `routes` table for a roomy context), checks that the input is left
 bit for bit unchanged, and repeats the call with out= the start of a larger sentinel-filled buffer: the result must be bit-identical
 and nothing past it may change.  Shapes: batch counts of 1, lines-per-workgroup +- 1 and more than one wave over 256 CUs; inner extents
 ragged for every column tile width (8 .. 256); odd inner extents on the real four-step; 3-d / 4-d tensors and trailing unit
@@ -43,7 +43,7 @@ def _sync(dsc):
     dsc.synchronize()
 
 
-# ---------------------------------------------------------------------------------------------------- run_job's routing, restated
+# ------------------------------------------------------------------------------------- the routes table of fft_driver.cpp, restated
 
 def _tile_width(L, sp):                                 # fft_regs_cols.hip cols_tile_width
     if L <= 32:
@@ -97,7 +97,7 @@ def _last_axis(L, mode, sp, x_n, in_len):
 
 
 def expect(kind, x_dt, shape, n, axis):
-    """the path dsc.last_fft_path() reports for kind(x, n, axis) in a roomy context (fft_driver.cpp run_job)"""
+    """the path dsc.last_fft_path() reports for kind(x, n, axis) in a roomy context (fft_driver.cpp, the route functions in the order of `routes`)"""
     x_dt = np.dtype(x_dt)
     axis = axis % len(shape)
     sp = real_of(x_dt) == F32
@@ -454,7 +454,7 @@ def _tight(kind, rows, cols, dt, need, spare, roomy):
 
 def test_real_axis_four_step_in_a_tight_context(record_property):
     """dsc_rfft along axis 0 of f32 [16384, 32]: cols_4step_real, whose tables include the 16384-point COMPLEX plan (not the 8192-point
-    REAL plan run_job makes).  Main arena, 256-B aligned blocks, plans carved from the top:
+    REAL plan geom_of makes for the job).  Main arena, 256-B aligned blocks, plans carved from the top:
         x      16384 * 32 * 4                      = 2097152
         out    8193 * 32 * 8                       = 2097408
         plan   REAL 8192, f32: 8192 * 8 + 8193 * 8 -> 65536 + 65792 = 131328
@@ -472,7 +472,7 @@ def test_real_axis_four_step_in_a_tight_context(record_property):
 
 def test_complex_axis_four_step_in_a_tight_context(record_property):
     """dsc_fft along axis 0 of c64 [16384, 16]: cols_4step with n1 = 256, n2 = 64 (16 columns widen the split), whose new tables are the
-    256- and 64-point plans (2048 + 512 B); the 16384-point plan is run_job's own.  Main arena:
+    256- and 64-point plans (2048 + 512 B); the 16384-point plan is the job's own (geom_of).  Main arena:
         x      16384 * 16 * 8  = 2097152
         out    16384 * 16 * 8  = 2097152
         plan   COMPLEX 16384   = 131072
