@@ -124,8 +124,12 @@ extern "C" dsc_tensor *dsc_stft(dsc_ctx *ctx, const dsc_tensor *x, int n_fft, in
     // the last line compute their offsets from row `rows`).  A row too long for even one per launch takes the composed route below
     // (64-bit gather indices) at any n_fft.
     const bool fused_off = getenv("DSC_NO_STFT_FUSED") != nullptr;             // read at every call: tools/bench_stft.py interleaves the routes
-    const long long rows_per = ((long long) 0x7f000000 - (long long) n_fft * (long long) rb) / ((long long) T * (long long) rb) - 1;
-    if (!fused_off && dsc_stft_regs_supports(n_fft) && rows_per >= 1) {
+    long long rows_per = ((long long) 0x7f000000 - (long long) n_fft * (long long) rb) / ((long long) T * (long long) rb) - 1;
+    // An even number of rows per launch keeps every launch's first element even (as conv.cpp does), so that pairs the kernel finds
+    // aligned relative to its base are aligned in memory too; with odd T a row too long for two per launch takes the composed route.
+    if (rows_per > 1) rows_per &= ~1LL;
+    const bool launch_aligned = rows_per != 1 || rows == 1 || (T & 1) == 0;
+    if (!fused_off && dsc_stft_regs_supports(n_fft) && rows_per >= 1 && launch_aligned) {
         const dsc_fft_plan *plan = dsc_plan_fft(ctx, n_fft / 2, DSC_FFT_REAL, cdt);
         for (long long r = 0; r < rows; r += rows_per) {
             const long long nr = rows - r < rows_per ? rows - r : rows_per;

@@ -1,4 +1,5 @@
 """Shared test helpers: deterministic signals, golden-fixture access, error metrics."""
+import ctypes
 import hashlib
 import json
 import os
@@ -61,6 +62,18 @@ def assert_close(actual, expected, tol=None, what=''):
     tol = TOL[expected.dtype] if tol is None else tol
     e2, em = rel_l2(actual, expected), max_rel(actual, expected)
     assert e2 <= tol and em <= tol * 4, f'{what}: rel_l2={e2:.3e} max_rel={em:.3e} tol={tol:g}'
+
+
+def device_view(dsc, big, shape, dt):
+    """A Tensor of `shape` / numpy dtype `dt` over the start of the device buffer of `big` (not owned): the out= target of the GPU
+    route tests, which fill `big` with a sentinel and check that nothing past the view changes."""
+    from dsc_amd import _bindings as B
+    from dsc_amd.context import _get_ctx
+    from dsc_amd.dtype import NP_TO_DTYPE
+    dt = np.dtype(dt)
+    c_shape = (ctypes.c_int * len(shape))(*shape)
+    nbytes = int(np.prod(shape)) * dt.itemsize
+    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
 
 
 class Golden:

@@ -9,7 +9,6 @@ ragged for every column tile width (8 .. 256); odd inner extents on the real fou
 dimensions; zero padded and cropped lines (irfft: fewer and more bins than order + 1, imaginary parts in bins 0 and order); plain
 noise plus lines with a large DC offset or one strong tone.  Routes behind an environment switch run in a child process, as do the
 tight-context fallbacks of the axis four-step routes."""
-import ctypes
 import os
 import subprocess
 import sys
@@ -17,6 +16,7 @@ import sys
 import numpy as np
 import pytest
 
+from tests.helpers import device_view as _view
 from tests.test_fft_ref import TAU, fft_err, out_len, pow2, real_of, ref_fft
 
 pytestmark = pytest.mark.gpu
@@ -168,15 +168,6 @@ def _out_dtype(kind, x_dt):
     if kind == 'irfft':
         return real_of(x_dt)
     return CPX[real_of(x_dt)]
-
-
-def _view(dsc, big, shape, dt):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
-    c_shape = (ctypes.c_int * len(shape))(*shape)
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
 
 
 def run_case(dsc, record_property, kind, x, n, axis):

@@ -1,7 +1,10 @@
 """GPU tests of dsc.stft / dsc.istft and the window helpers against the numpy restatement of tests/test_stft_abi.py (f64 on the
-host): fused (stft_regs) and composed (stft_composed) sizes, every hop family (n/4, n/2, n, 2n, odd), center / not, reflect /
-constant padding, [T] / [B, T] / [2, 3, T] inputs, no / Hann / Kaiser / random asymmetric windows, the DSC_NO_STFT_FUSED switch, a
-tightly sized context, istft against torch.istft, round trips, NOLA, and one full-size [64, 2^20] case."""
+host), whole-array rel-L2: five of the fused (stft_regs) lengths — 64, 256, 1024, 4096, 32768 — and four composed (stft_composed)
+ones with the hop families n/4, n/2, n, 2n and odd; per (n_fft, hop, dtype) ONE draw of center, padding, shape ([T] / [B, T] /
+[2, 3, T]) and window (none / Hann / Kaiser / random asymmetric), the full product of those options at 256, 4096 and 32 only; the
+DSC_NO_STFT_FUSED switch, a tightly sized context, istft against torch.istft, round trips, NOLA, and one full-size [64, 2^20] case.
+Every fused length, every option at every length, the edges of the signal, workgroup geometry, the istft chunking branches and the
+out= / stray-write checks, per frame and per sample against a long-double reference, are in tests/test_gpu_stft_routes.py."""
 import itertools
 import json
 import os
