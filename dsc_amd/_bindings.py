@@ -178,6 +178,11 @@ dsc_rfft2 = _sig('dsc_rfft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p,
 dsc_irfft2 = _sig('dsc_irfft2', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
 dsc_hilbert = _sig('dsc_hilbert', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
 dsc_envelope = _sig('dsc_envelope', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
+dsc_upfirdn = _sig('dsc_upfirdn', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int, _DscTensor_p)
+dsc_resample_poly = _sig('dsc_resample_poly', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p, _DscTensor_p)
+dsc_decimate = _sig('dsc_decimate', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p)
+dsc_firwin = _sig('dsc_firwin', _DscTensor_p, _DscCtx, c_int, c_double, c_int, c_double, c_uint8)
+dsc_firwin_host = _sig('dsc_firwin_host', None, POINTER(c_double), c_int, c_double, c_int, c_double)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` and `dsc::hilbert / envelope`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope` and `dsc::upfirdn / resample_poly / decimate / firwin`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -265,6 +265,19 @@ template<typename T>
 static inline tensor<T> hilbert(const tensor<T> &x, int n = -1) noexcept { return dsc_hilbert(ctx, x.x_, nullptr, n); }
 template<typename T>
 static inline tensor<T> envelope(const tensor<T> &x, int n = -1) noexcept { return dsc_envelope(ctx, x.x_, nullptr, n); }
+
+// Section H of dsc_mi355x.h: polyphase FIR resampling along the last axis (scipy.signal.upfirdn / resample_poly / decimate with
+// ftype='fir') and the low-pass window design; window 0 = hamming, 1 = kaiser
+template<typename T>
+static inline tensor<T> upfirdn(const tensor<T> &h, const tensor<T> &x, int up = 1, int down = 1) noexcept { return dsc_upfirdn(ctx, h.x_, x.x_, up, down, nullptr); }
+template<typename T>
+static inline tensor<T> resample_poly(const tensor<T> &x, int up, int down) noexcept { return dsc_resample_poly(ctx, x.x_, up, down, nullptr, nullptr); }
+template<typename T>
+static inline tensor<T> resample_poly(const tensor<T> &x, int up, int down, const tensor<T> &taps) noexcept { return dsc_resample_poly(ctx, x.x_, up, down, taps.x_, nullptr); }
+template<typename T>
+static inline tensor<T> decimate(const tensor<T> &x, int q, int n = 0) noexcept { return dsc_decimate(ctx, x.x_, q, n, nullptr); }
+template<typename T>
+static inline tensor<T> firwin(int numtaps, double cutoff, int window = 0, double beta = 5.0) noexcept { return dsc_firwin(ctx, numtaps, cutoff, window, beta, dtype_of<T>::value); }
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

@@ -230,6 +230,15 @@ void dsc_launch_hilbert_zip(const void *x, const void *y, void *out, long long q
 void dsc_launch_hilbert_widen(const void *x, void *xw, long long q0, long long n_lines, long long in_pitch, int in_len, int wpitch,
                               hipStream_t stream);
 
+// ---- polyphase FIR resampling (dsc_upfirdn / dsc_resample_poly / dsc_decimate, resample.cpp) -----
+// Direct kernel (polyphase.hip): y[r][m] = sum_i (h[t - i up] gain) x[r][i], t = m down + t0, over 0 <= i < T and 0 <= t - i up < M, for
+// 0 <= m < T_out; x [rows][T], h [M], y [rows][T_out] reals of one precision; up, down, M >= 1, t0 >= 0, rows T_out < 2^31.  The taps are
+// multiplied by gain once, in the data's precision.  Returns false, with nothing launched, when the taps and the samples of even a
+// 64-output tile do not fit dsc_polyphase_lds_limit() bytes of LDS.  y must not overlap x.
+size_t dsc_polyphase_lds_limit();
+bool dsc_launch_polyphase(const void *x, const void *h, void *y, long long rows, long long T, long long T_out, int M, int up, int down, long long t0,
+                          double gain, bool single_precision, hipStream_t stream);
+
 // ---- 2-D transforms of small images (dsc_fft2 / dsc_ifft2 / dsc_rfft2, fft2.cpp) -----------------
 // One pass (fft_2d.hip): in [n_img][h][w] (complex for C2C, reals for R2C_CAST and R2C_PACKED), zero padded / cropped to N0 x N1,
 // out [n_img][N0][N1] complex (R2C_PACKED: [n_img][N0][N1/2 + 1]).  N0, N1 in {32, 64, 128} (R2C_PACKED: N1 in {64, 128, 256}).

@@ -437,6 +437,38 @@ def envelope(x: Tensor, n: Union[int, None] = -1, out: Union[Tensor, None] = Non
     return _hilbert_like(B.dsc_envelope, x, n, out)
 
 
+# ---- polyphase FIR resampling along the last axis (include/dsc_mi355x.h, Section H): scipy.signal.upfirdn / resample_poly / decimate
+# (ftype='fir') and the low-pass firwin, in one pass of the direct kernel; nothing is rounded to a power of two
+
+_FIRWIN_WINDOWS = {'hamming': 0, 'kaiser': 1}
+
+
+def upfirdn(h: Tensor, x: Tensor, up: int = 1, down: int = 1, out: Union[Tensor, None] = None) -> Tensor:
+    """Upsample every row of real x [.., T] by `up` (zero stuffing), filter with real h [M] of the same dtype, keep every `down`-th
+    sample: ceil(((T - 1) up + M) / down) samples per row.  scipy.signal.upfirdn(h, x, up, down, axis=-1)."""
+    return Tensor(B.dsc_upfirdn(_get_ctx(), h._c_ptr, x._c_ptr, int(up), int(down), _c_ptr_or_none(out)), out is not None)
+
+
+def resample_poly(x: Tensor, up: int, down: int, taps: Union[Tensor, None] = None, out: Union[Tensor, None] = None) -> Tensor:
+    """Resample every row of real x [.., T] to ceil(T up / down) samples with a zero-phase low-pass FIR: the Kaiser (beta 5) design of
+    20 max(up, down) + 1 taps, or the caller's taps (scipy's window=array).  scipy.signal.resample_poly(x, up, down, axis=-1)."""
+    return Tensor(B.dsc_resample_poly(_get_ctx(), x._c_ptr, int(up), int(down), _c_ptr_or_none(taps), _c_ptr_or_none(out)), out is not None)
+
+
+def decimate(x: Tensor, q: int, n: Union[int, None] = None, out: Union[Tensor, None] = None) -> Tensor:
+    """Low-pass (Hamming FIR of order n, default 20 q) and keep every q-th sample, zero phase.
+    scipy.signal.decimate(x, q, n, ftype='fir')."""
+    return Tensor(B.dsc_decimate(_get_ctx(), x._c_ptr, int(q), 0 if n is None else int(n), _c_ptr_or_none(out)), out is not None)
+
+
+def firwin(numtaps: int, cutoff: float, window: str = 'hamming', beta: float = 5.0, dtype: Dtype = Dtype.F32) -> Tensor:
+    """Low-pass FIR design by the window method: scipy.signal.firwin(numtaps, cutoff, window='hamming' or ('kaiser', beta)), cutoff
+    as a fraction of the Nyquist frequency, unit gain at DC."""
+    if window not in _FIRWIN_WINDOWS:
+        raise ValueError(f"firwin: window must be 'hamming' or 'kaiser', got {window!r}")
+    return Tensor(B.dsc_firwin(_get_ctx(), int(numtaps), float(cutoff), _FIRWIN_WINDOWS[window], float(beta), dtype.value))
+
+
 def filter_fft(s: Tensor, H: Tensor, out=None) -> Tensor:
     """irfft(rfft(s, n) * H) with n = 2 * (len(H) - 1), fused where a kernel exists."""
     return Tensor(B.dsc_filter_fft(_get_ctx(), s._c_ptr, H._c_ptr, _c_ptr_or_none(out)), out is not None)

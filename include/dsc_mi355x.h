@@ -344,6 +344,45 @@ dsc_tensor *dsc_hilbert (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int
 dsc_tensor *dsc_envelope(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section H — polyphase FIR resampling (no reference counterpart).
+ *
+ * Along the LAST axis of x real [.., T] (f32 or f64, at most 4 dims); h real [M] of x's dtype, broadcast over the rows.  Nothing is
+ * rounded to a power of two.  All three operators are one primitive P(x, h, gain, up, down, t0, T_out):
+ *   y[r][m] = sum_i (h[t - i up] gain) x[r][i],   t = m down + t0 (64-bit),   over every i with 0 <= i < T and 0 <= t - i up < M,
+ *   for 0 <= m < T_out.  The taps are multiplied by gain once, in x's dtype (one rounding: scipy's h * up); accumulation is in x's
+ *   dtype; no atomics, every output written once: results are deterministic.
+ *   dsc_upfirdn(h, x, up, down)          gain 1, t0 0, T_out = ceil(((T - 1) up + M) / down): scipy.signal.upfirdn(h, x, up, down, axis=-1)
+ *   dsc_resample_poly(x, up, down, taps) up and down are first divided by their gcd.  1 / 1 is a copy of x (scipy's early return).
+ *                                        Otherwise T_out = ceil(T up / down), gain up, t0 = half_len; taps NULL: half_len =
+ *                                        10 max(up, down), h = dsc_firwin(2 half_len + 1, 1 / max(up, down), kaiser, beta 5) in x's
+ *                                        dtype; taps [M] (scipy's window=array): half_len = (M - 1) / 2.
+ *                                        scipy.signal.resample_poly(x, up, down, axis=-1[, window=taps]).
+ *   dsc_decimate(x, q, n)                dsc_resample_poly(x, 1, q, dsc_firwin(n + 1, 1 / q, hamming)), n = 20 q when n <= 0; q >= 2:
+ *                                        scipy.signal.decimate(x, q, n, ftype='fir', zero_phase=True)
+ *   dsc_firwin(numtaps, cutoff, window, beta, dtype)   the low-pass design scipy.signal.firwin(numtaps, cutoff, window=..,
+ *                                        pass_zero=True, scale=True) with fs = 2: h[k] = cutoff sinc(cutoff (k - alpha)) w[k],
+ *                                        alpha = (numtaps - 1) / 2, divided by sum h; window 0 = symmetric Hamming
+ *                                        0.54 - 0.46 cos(2 pi k / (numtaps - 1)), 1 = symmetric Kaiser
+ *                                        I0(beta sqrt(1 - ((k - alpha) / alpha)^2)) / I0(beta); 0 < cutoff < 1.  Designed on the host in
+ *                                        long double, rounded once to dtype (f32 / f64), uploaded on the context's stream (it
+ *                                        synchronises, as dsc_randn does).  Designs are not cached: pass `taps` to reuse one.
+ * out: NULL or a tensor of the result's shape and dtype; it must not share memory with x.  Argument errors (complex input, up or
+ * down < 1, M < 1, a dtype mismatch, a wrong out, out overlapping x, a result of more than 2^31 - 1 elements, q < 2, a cutoff outside
+ * (0, 1)) print and exit like every operator.
+ * dsc_last_fft_path: "polyphase_direct" — ONE pass of the direct kernel (polyphase.hip): a workgroup stages the taps (phase-major, times
+ * gain) and the samples of a tile of consecutive outputs in LDS and forms K = ceil(M / up) products per output; no scratch.  The host
+ * sizes the tile to the LDS; when the taps and the samples of even a 64-output tile exceed 160 KiB (about down (64 + M / up) + M + 4 up
+ * elements) the call is an argument error.  Guaranteed to run in both dtypes: every reduced (up, down) with max(up, down) <= 160 with the
+ * designed filters, and any M <= 4096 with up, down <= 16.  "polyphase_copy": dsc_resample_poly whose reduced rates are 1 / 1.
+ */
+dsc_tensor *dsc_upfirdn      (dsc_ctx *ctx, const dsc_tensor *h, const dsc_tensor *x, int up, int down, dsc_tensor *out);
+dsc_tensor *dsc_resample_poly(dsc_ctx *ctx, const dsc_tensor *x, int up, int down, const dsc_tensor *taps, dsc_tensor *out);
+dsc_tensor *dsc_decimate     (dsc_ctx *ctx, const dsc_tensor *x, int q, int n, dsc_tensor *out);
+dsc_tensor *dsc_firwin       (dsc_ctx *ctx, int numtaps, double cutoff, int window, double beta, dsc_dtype dtype);
+/* host only, needs no device: the design dsc_firwin uploads, in double before the rounding to dtype */
+void        dsc_firwin_host  (double *taps, int numtaps, double cutoff, int window, double beta);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
