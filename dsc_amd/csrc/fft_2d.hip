@@ -23,7 +23,7 @@
 // N1 / 2 need no special treatment in this form: they fall out of the same formula.  Spectrum rows have the odd pitch M + 1.
 //
 // The inverse real transform (dsc_irfft2) is not fused: fft2.cpp composes it from dsc_ifft and dsc_irfft.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -257,43 +257,14 @@ __global__ __launch_bounds__((fft2_cfg<R, N0, M>::NT)) void fft2_kernel(const vo
     }
 }
 
-template<typename R, int N0, int M, bool REAL, bool INV>
-void launch_fft2_one(const void *in, void *out, long long n_img, int h, int w, bool in_real, double scale, hipStream_t stream) {
-    using cfg = fft2_cfg<R, N0, M>;
-    static_assert(cfg::LDS <= 160 * 1024, "one image plane and the table fit the LDS of a CU");
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft2_kernel<R, N0, M, REAL, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) cfg::LDS));
+// side of the window -> N0 or M of fft2_kernel; a size without a kernel ends the process
+template<typename F> void with_fft2_len(int n, F f) {
+    switch (n) {
+        case 32:  return f(int_c<32>{});
+        case 64:  return f(int_c<64>{});
+        case 128: return f(int_c<128>{});
     }
-    const long long groups = (n_img + cfg::G - 1) / cfg::G;
-    DSC_LAUNCH((fft2_kernel<R, N0, M, REAL, INV>), dim3((unsigned) groups), dim3(cfg::NT), cfg::LDS, stream, in, out, n_img, h, w, in_real ? 1 : 0,
-               ((w & 1) == 0 && ((size_t) in & (2 * sizeof(R) - 1)) == 0) ? 1 : 0, (R) scale);
-}
-
-template<typename R, int N0, int M>
-void launch_fft2_mode(const void *in, void *out, long long n_img, int h, int w, dsc_fft_mode mode, bool inverse, double scale, hipStream_t stream) {
-    if (mode == DSC_MODE_R2C_PACKED) launch_fft2_one<R, N0, M, true, false>(in, out, n_img, h, w, true, scale, stream);
-    else if (inverse)                launch_fft2_one<R, N0, M, false, true>(in, out, n_img, h, w, mode == DSC_MODE_R2C_CAST, scale, stream);
-    else                             launch_fft2_one<R, N0, M, false, false>(in, out, n_img, h, w, mode == DSC_MODE_R2C_CAST, scale, stream);
-}
-
-template<typename R, int N0>
-void launch_fft2_cols(int M, const void *in, void *out, long long n_img, int h, int w, dsc_fft_mode mode, bool inverse, double scale, hipStream_t stream) {
-    switch (M) {
-        case 32: launch_fft2_mode<R, N0, 32>(in, out, n_img, h, w, mode, inverse, scale, stream); break;
-        case 64: launch_fft2_mode<R, N0, 64>(in, out, n_img, h, w, mode, inverse, scale, stream); break;
-        default: launch_fft2_mode<R, N0, 128>(in, out, n_img, h, w, mode, inverse, scale, stream); break;
-    }
-}
-
-template<typename R>
-void launch_fft2_rows(int N0, int M, const void *in, void *out, long long n_img, int h, int w, dsc_fft_mode mode, bool inverse, double scale,
-                      hipStream_t stream) {
-    switch (N0) {
-        case 32: launch_fft2_cols<R, 32>(M, in, out, n_img, h, w, mode, inverse, scale, stream); break;
-        case 64: launch_fft2_cols<R, 64>(M, in, out, n_img, h, w, mode, inverse, scale, stream); break;
-        default: launch_fft2_cols<R, 128>(M, in, out, n_img, h, w, mode, inverse, scale, stream); break;
-    }
+    no_kernel("fft_2d.hip", "window side", n);
 }
 
 constexpr bool is_fused_dim(int n) { return n == 32 || n == 64 || n == 128; }
@@ -314,6 +285,16 @@ void dsc_launch_fft2_regs(const void *in, void *out, long long n_img, int N0, in
                           bool single_precision, double scale, hipStream_t stream) {
     if (n_img <= 0) return;
     const int M = mode == DSC_MODE_R2C_PACKED ? N1 / 2 : N1;
-    if (single_precision) launch_fft2_rows<float>(N0, M, in, out, n_img, h, w, mode, inverse, scale, stream);
-    else                  launch_fft2_rows<double>(N0, M, in, out, n_img, h, w, mode, inverse, scale, stream);
+    const bool real = mode == DSC_MODE_R2C_PACKED;                 // R2C_CAST: the C2C kernel, widening while it loads
+    if (mode == DSC_MODE_C2R_PACKED) no_kernel("fft_2d.hip", "transform mode", mode);
+    with_real(single_precision, [&](auto r) { with_fft2_len(N0, [&](auto n0) { with_fft2_len(M, [&](auto m) {
+        with_mode(real ? DSC_MODE_R2C_PACKED : DSC_MODE_C2C, inverse, [&](auto md, auto inv) {
+            using R = decltype(r);
+            using cfg = fft2_cfg<R, decltype(n0)::value, decltype(m)::value>;
+            static_assert(cfg::LDS <= 160 * 1024, "one image plane and the table fit the LDS of a CU");
+            dsc_launch_dyn_lds<fft2_kernel<R, decltype(n0)::value, decltype(m)::value, decltype(md)::value == DSC_MODE_R2C_PACKED, decltype(inv)::value>>(
+                (unsigned) ((n_img + cfg::G - 1) / cfg::G), cfg::NT, cfg::LDS, stream, in, out, n_img, h, w, mode == DSC_MODE_C2C ? 0 : 1,
+                ((w & 1) == 0 && ((size_t) in & (2 * sizeof(R) - 1)) == 0) ? 1 : 0, (R) scale);
+        });
+    }); }); });
 }

@@ -67,16 +67,9 @@ __global__ __launch_bounds__(1024) void c2c32k_kernel(const f2 *__restrict__ z, 
 void dsc_launch_fft32k_c32(const void *z, void *Z, int batch, int in_pitch, int in_len, bool inverse, bool cast, const void *aux, int n_cu,
                            hipStream_t stream) {
     if (batch <= 0) return;
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) c2c32k_kernel<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) c2c32k_kernel<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) c2c32k_kernel<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) c2c32k_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-    }
     const int grid = batch < n_cu ? batch : n_cu;
-#define C2C32K(INV, CAST) DSC_LAUNCH((c2c32k_kernel<INV, CAST>), dim3(grid), dim3(1024), kLdsBytes, stream, (const f2 *) z, (f2 *) Z, batch, (const f2 *) aux, in_pitch, in_len)
-    if (inverse) { if (cast) C2C32K(true, true); else C2C32K(true, false); }
-    else         { if (cast) C2C32K(false, true); else C2C32K(false, false); }
-#undef C2C32K
+    with_bool(inverse, [&](auto inv) { with_bool(cast, [&](auto c) {
+        dsc_launch_dyn_lds<c2c32k_kernel<decltype(inv)::value, decltype(c)::value>>(grid, 1024, kLdsBytes, stream, (const f2 *) z, (f2 *) Z, batch,
+                                                                                    (const f2 *) aux, in_pitch, in_len);
+    }); });
 }

@@ -17,7 +17,7 @@
 //
 // The 65536-point f32 real transforms do not come here: fft_r2c_64k.hip keeps the whole
 // transform in registers.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -302,21 +302,9 @@ void launch_lines(const dsc_fft_lines_args &a, dsc_fft_mode mode, hipStream_t st
     const int threads = points <= 256 ? 64 : points <= 2048 ? 256 : points <= 8192 ? 512 : 1024;
     const long long tiles = (a.n_lines + C - 1) / C;
     const size_t lds = 2 * (size_t) p.C * p.P * sizeof(cx<T>) + (size_t) p.C * 20;      // two images + per-line base tables
-    dim3 grid((unsigned) tiles), block(threads);
-    static unsigned long long attr_devices = 0;          // dynamic LDS above 64 KiB must be opted into, once per kernel
-    if (dsc_first_use_on_device(attr_devices)) {
-        const int max_lds = 2 * kTileBytes + 8192;
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_lines_kernel<T, DSC_MODE_C2C>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_lines_kernel<T, DSC_MODE_R2C_CAST>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_lines_kernel<T, DSC_MODE_R2C_PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_lines_kernel<T, DSC_MODE_C2R_PACKED>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds));
-    }
-    switch (mode) {
-        case DSC_MODE_C2C:        DSC_LAUNCH((fft_lines_kernel<T, DSC_MODE_C2C>), grid, block, lds, stream, p); break;
-        case DSC_MODE_R2C_CAST:   DSC_LAUNCH((fft_lines_kernel<T, DSC_MODE_R2C_CAST>), grid, block, lds, stream, p); break;
-        case DSC_MODE_R2C_PACKED: DSC_LAUNCH((fft_lines_kernel<T, DSC_MODE_R2C_PACKED>), grid, block, lds, stream, p); break;
-        case DSC_MODE_C2R_PACKED: DSC_LAUNCH((fft_lines_kernel<T, DSC_MODE_C2R_PACKED>), grid, block, lds, stream, p); break;
-    }
+    with_mode(mode, false, [&](auto m, auto) {            // two images of kTileBytes at the most, plus the base tables
+        dsc_launch_var_lds<fft_lines_kernel<T, decltype(m)::value>, 2 * kTileBytes + 8192>((unsigned) tiles, threads, lds, stream, p);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -416,56 +404,44 @@ int dsc_fft_lds_max_len(bool single_precision) {
 
 void dsc_launch_fft_lines(const dsc_fft_lines_args &a, dsc_fft_mode mode, bool single_precision, hipStream_t stream) {
     if (a.n_lines <= 0) return;
-    if (single_precision) launch_lines<float>(a, mode, stream);
-    else                  launch_lines<double>(a, mode, stream);
+    with_real(single_precision, [&](auto real) { launch_lines<decltype(real)>(a, mode, stream); });
 }
 
+// pack: the two packed-real modes share the pair-up form
 void dsc_launch_fft_pack(const void *in, void *work, long long q_first, long long n_lines, long long inner, dsc_line_layout lin,
                          int L, int in_len, dsc_fft_mode mode, bool sp, hipStream_t stream) {
-    const dim3 grid = flat_grid(n_lines * L), block(256);
-#define PACK(T, M) DSC_LAUNCH((fft_pack_kernel<T, M>), grid, block, 0, stream, in, (cx<T> *) work, q_first, n_lines, inner, lin, L, in_len)
-    if (sp) {
-        if (mode == DSC_MODE_C2C) PACK(float, DSC_MODE_C2C);
-        else if (mode == DSC_MODE_R2C_CAST) PACK(float, DSC_MODE_R2C_CAST);
-        else PACK(float, DSC_MODE_R2C_PACKED);
-    } else {
-        if (mode == DSC_MODE_C2C) PACK(double, DSC_MODE_C2C);
-        else if (mode == DSC_MODE_R2C_CAST) PACK(double, DSC_MODE_R2C_CAST);
-        else PACK(double, DSC_MODE_R2C_PACKED);
-    }
-#undef PACK
+    with_real(sp, [&](auto real) { with_mode(mode, false, [&](auto m, auto) {
+        using T = decltype(real);
+        constexpr int M = decltype(m)::value == DSC_MODE_C2R_PACKED ? DSC_MODE_R2C_PACKED : decltype(m)::value;
+        DSC_LAUNCH((fft_pack_kernel<T, M>), flat_grid(n_lines * L), dim3(256), 0, stream, in, (cx<T> *) work, q_first, n_lines, inner, lin, L,
+                   in_len);
+    }); });
 }
 
 void dsc_launch_fft_c2r_prepass(const void *in, void *work, long long q_first, long long n_lines, long long inner, dsc_line_layout lin,
                                 int L, int in_len, const void *tw_real, bool sp, hipStream_t stream) {
-    const dim3 grid = flat_grid(n_lines * L), block(256);
-    if (sp) DSC_LAUNCH(fft_c2r_prepass_kernel<float>, grid, block, 0, stream, (const cx<float> *) in, (cx<float> *) work,
-                               q_first, n_lines, inner, lin, L, in_len, (const cx<float> *) tw_real);
-    else    DSC_LAUNCH(fft_c2r_prepass_kernel<double>, grid, block, 0, stream, (const cx<double> *) in, (cx<double> *) work,
-                               q_first, n_lines, inner, lin, L, in_len, (const cx<double> *) tw_real);
+    with_real(sp, [&](auto real) {
+        using T = decltype(real);
+        DSC_LAUNCH(fft_c2r_prepass_kernel<T>, flat_grid(n_lines * L), dim3(256), 0, stream, (const cx<T> *) in, (cx<T> *) work, q_first, n_lines, inner, lin,
+                   L, in_len, (const cx<T> *) tw_real);
+    });
 }
 
 void dsc_launch_fft_r2c_postpass(const void *work, void *out, long long q_first, long long n_lines, long long inner, dsc_line_layout lout,
                                  int L, const void *tw_real, bool sp, hipStream_t stream) {
-    const dim3 grid = flat_grid(n_lines * (L + 1LL)), block(256);
-    if (sp) DSC_LAUNCH(fft_r2c_postpass_kernel<float>, grid, block, 0, stream, (const cx<float> *) work, (cx<float> *) out,
-                               q_first, n_lines, inner, lout, L, (const cx<float> *) tw_real);
-    else    DSC_LAUNCH(fft_r2c_postpass_kernel<double>, grid, block, 0, stream, (const cx<double> *) work, (cx<double> *) out,
-                               q_first, n_lines, inner, lout, L, (const cx<double> *) tw_real);
+    with_real(sp, [&](auto real) {
+        using T = decltype(real);
+        DSC_LAUNCH(fft_r2c_postpass_kernel<T>, flat_grid(n_lines * (L + 1LL)), dim3(256), 0, stream, (const cx<T> *) work, (cx<T> *) out, q_first, n_lines,
+                   inner, lout, L, (const cx<T> *) tw_real);
+    });
 }
 
+// unpack: every mode but C2R_PACKED writes complex values
 void dsc_launch_fft_unpack(const void *work, void *out, long long q_first, long long n_lines, long long inner, dsc_line_layout lout,
                            int L, double scale, dsc_fft_mode mode, bool sp, hipStream_t stream) {
-    const dim3 grid = flat_grid(n_lines * L), block(256);
-    if (sp) {
-        if (mode == DSC_MODE_C2R_PACKED)
-            DSC_LAUNCH((fft_unpack_kernel<float, DSC_MODE_C2R_PACKED>), grid, block, 0, stream, (const cx<float> *) work, out, q_first, n_lines, inner, lout, L, (float) scale);
-        else
-            DSC_LAUNCH((fft_unpack_kernel<float, DSC_MODE_C2C>), grid, block, 0, stream, (const cx<float> *) work, out, q_first, n_lines, inner, lout, L, (float) scale);
-    } else {
-        if (mode == DSC_MODE_C2R_PACKED)
-            DSC_LAUNCH((fft_unpack_kernel<double, DSC_MODE_C2R_PACKED>), grid, block, 0, stream, (const cx<double> *) work, out, q_first, n_lines, inner, lout, L, scale);
-        else
-            DSC_LAUNCH((fft_unpack_kernel<double, DSC_MODE_C2C>), grid, block, 0, stream, (const cx<double> *) work, out, q_first, n_lines, inner, lout, L, scale);
-    }
+    with_real(sp, [&](auto real) { with_bool(mode == DSC_MODE_C2R_PACKED, [&](auto c2r) {
+        using T = decltype(real);
+        DSC_LAUNCH((fft_unpack_kernel<T, decltype(c2r)::value ? DSC_MODE_C2R_PACKED : DSC_MODE_C2C>), flat_grid(n_lines * L), dim3(256), 0, stream,
+                   (const cx<T> *) work, out, q_first, n_lines, inner, lout, L, (T) scale);
+    }); });
 }

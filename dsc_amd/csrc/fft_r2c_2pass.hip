@@ -19,7 +19,7 @@
 //                block); partners meet through an LDS staging plane, one component at a time.
 // Twice the algorithmic traffic (the ceiling is half the copy rate).  The inverse runs the same two kernels backwards.
 // Reference: dsc_rfft / dsc_irfft (dsc/src/dsc.cpp:2102-2260, dsc_fft.h:57-238).
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -370,13 +370,6 @@ void launch_pair(const void *in, void *out, long long rows, void *work, const vo
     using C = cpx<R>;
     constexpr int L = 32 * B1 * 1024;
     constexpr int rl = rows_lds_bytes<R>(), cl = cols_lds_bytes<R, B1>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) two_pass_rows_kernel<R, B1, false, CAST>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) two_pass_rows_kernel<R, B1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, rl));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) two_pass_cols_kernel<R, B1, false, REAL>, hipFuncAttributeMaxDynamicSharedMemorySize, cl));
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) two_pass_cols_kernel<R, B1, true, REAL, CAST>, hipFuncAttributeMaxDynamicSharedMemorySize, cl));
-    }
     const dim3 grid((unsigned) (rows * 2 * B1));          // L1 / 16 row groups per transform
     constexpr int CT = cols_threads<R, B1>();
     const dim3 cgrid((unsigned) (rows * (1024 / (CT / B1))));   // 1024 / NC column blocks per transform
@@ -384,31 +377,36 @@ void launch_pair(const void *in, void *out, long long rows, void *work, const vo
     constexpr long long full_row_b = (long long) L * sizeof(C);
     constexpr int out_bins = REAL ? L + 1 : L;
     if (!inverse) {
-        DSC_LAUNCH((two_pass_rows_kernel<R, B1, false, CAST>), grid, dim3(512), rl, stream, (const C *) in, (C *) work, (const C *) tw_full, (R) 1,
-                           in_pitch * ext_b, (int) (in_len * ext_b));
-        DSC_LAUNCH((two_pass_cols_kernel<R, B1, false, REAL>), cgrid, dim3(CT), cl, stream, (const C *) work, (C *) out, (const C *) tw_full,
-                           (const C *) tw_real, (long long) out_bins, out_bins);
+        dsc_launch_dyn_lds<two_pass_rows_kernel<R, B1, false, CAST>>(grid, 512, rl, stream, (const C *) in, (C *) work, (const C *) tw_full, (R) 1,
+                                                                     in_pitch * ext_b, (int) (in_len * ext_b));
+        dsc_launch_dyn_lds<two_pass_cols_kernel<R, B1, false, REAL>>(cgrid, CT, cl, stream, (const C *) work, (C *) out, (const C *) tw_full,
+                                                                     (const C *) tw_real, (long long) out_bins, out_bins);
     } else {
-        DSC_LAUNCH((two_pass_cols_kernel<R, B1, true, REAL, CAST>), cgrid, dim3(CT), cl, stream, (const C *) in, (C *) work, (const C *) tw_full,
-                           (const C *) tw_real, in_pitch, in_len);
-        DSC_LAUNCH((two_pass_rows_kernel<R, B1, true>), grid, dim3(512), rl, stream, (const C *) work, (C *) out, (const C *) tw_full,
-                           (R) (1.0 / (double) L), full_row_b, (int) full_row_b);                 // 2/(2n) (dsc_fft.h:232) = 1/n (:168-175)
+        dsc_launch_dyn_lds<two_pass_cols_kernel<R, B1, true, REAL, CAST>>(cgrid, CT, cl, stream, (const C *) in, (C *) work, (const C *) tw_full,
+                                                                          (const C *) tw_real, in_pitch, in_len);
+        dsc_launch_dyn_lds<two_pass_rows_kernel<R, B1, true>>(grid, 512, rl, stream, (const C *) work, (C *) out, (const C *) tw_full,
+                                                              (R) (1.0 / (double) L), full_row_b, (int) full_row_b);      // 2/(2n) (dsc_fft.h:232) = 1/n (:168-175)
     }
 }
 
+// complex length -> (B1, CAST) of launch_pair (L = 32768 B1), CAST (real rows through dsc_fft) at 262144 only; anything else ends the process
 template<typename R, bool REAL>
 void launch_len(int L, bool cast, const void *in, void *out, long long rows, void *work, const void *tw_full, const void *tw_real, bool inverse,
                 long long in_pitch, int in_len, hipStream_t stream) {
+    const auto pair = [&](auto b1, auto c) {
+        launch_pair<R, decltype(b1)::value, REAL, decltype(c)::value>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream);
+    };
+    if (cast && (REAL || L != 262144)) no_kernel("fft_r2c_2pass.hip", "real rows widened at complex length", L);
     switch (L) {
-        case 32768:  launch_pair<R, 1, REAL>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break;
-        case 65536:  launch_pair<R, 2, REAL>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break;
-        case 131072: launch_pair<R, 4, REAL>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break;
-        case 524288: launch_pair<R, 16, REAL>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break;
-        case 1048576: launch_pair<R, 32, REAL>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break;
-        default:
-            if constexpr (!REAL) { if (cast) { launch_pair<R, 8, false, true>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break; } }
-            launch_pair<R, 8, REAL>(in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream); break;
+        case 32768:   return pair(int_c<1>{}, bool_c<false>{});
+        case 65536:   return pair(int_c<2>{}, bool_c<false>{});
+        case 131072:  return pair(int_c<4>{}, bool_c<false>{});
+        case 262144:  if constexpr (!REAL) { if (cast) return pair(int_c<8>{}, bool_c<true>{}); }
+                      return pair(int_c<8>{}, bool_c<false>{});
+        case 524288:  return pair(int_c<16>{}, bool_c<false>{});
+        case 1048576: return pair(int_c<32>{}, bool_c<false>{});
     }
+    no_kernel("fft_r2c_2pass.hip", "complex length", L);
 }
 
 }  // namespace
@@ -424,8 +422,9 @@ bool dsc_fft_two_pass_supports(int L, bool single_precision) {
 void dsc_launch_rfft_two_pass(const void *in, void *out, long long rows, int L, bool inverse, bool single_precision, void *work,
                               const void *tw_full, const void *tw_real, long long in_pitch, int in_len, hipStream_t stream) {
     if (rows <= 0) return;
-    if (single_precision) launch_len<float, true>(L, false, in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream);
-    else                  launch_len<double, true>(L, false, in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream);
+    with_real(single_precision, [&](auto real) {
+        launch_len<decltype(real), true>(L, false, in, out, rows, work, tw_full, tw_real, inverse, in_pitch, in_len, stream);
+    });
 }
 
 // complex transforms of the same lengths: in = [rows][in_pitch] complex of which in_len <= L are transformed, out = [rows][L]
@@ -433,6 +432,7 @@ void dsc_launch_rfft_two_pass(const void *in, void *out, long long rows, int L, 
 void dsc_launch_fft_two_pass(const void *in, void *out, long long rows, int L, bool inverse, bool cast, bool single_precision, void *work,
                              const void *tw_full, long long in_pitch, int in_len, hipStream_t stream) {
     if (rows <= 0) return;
-    if (single_precision) launch_len<float, false>(L, cast, in, out, rows, work, tw_full, tw_full, inverse, in_pitch, in_len, stream);
-    else                  launch_len<double, false>(L, cast, in, out, rows, work, tw_full, tw_full, inverse, in_pitch, in_len, stream);
+    with_real(single_precision, [&](auto real) {
+        launch_len<decltype(real), false>(L, cast, in, out, rows, work, tw_full, tw_full, inverse, in_pitch, in_len, stream);
+    });
 }

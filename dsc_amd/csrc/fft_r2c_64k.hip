@@ -27,7 +27,7 @@
 // twiddles come from an 8 KiB LDS table indexed by the two factors of the exponent,
 // T[r][h] = W_1024^{r h} (r = register, a constant; h = per-thread), and two per-thread constants.
 // The inverse kernel (dsc_irfft, dsc_fft.h:194-236) is the same pipeline run backwards.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -1049,31 +1049,19 @@ void dsc_r2c64k_build_tables(void *host_dst) {
 
 void dsc_launch_rfft64k(const float *x, void *X, int batch, int in_pitch, int in_len, const void *aux, int n_cu, hipStream_t stream) {
     if (batch <= 0) return;
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) rfft64k_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-    }
     const int grid = batch < n_cu ? batch : n_cu;
-    DSC_LAUNCH(rfft64k_kernel, dim3(grid), dim3(1024), kLdsBytes, stream, x, (f2 *) X, batch, (const f2 *) aux, in_pitch, in_len PROBE_NULL);
+    dsc_launch_dyn_lds<rfft64k_kernel>(grid, 1024, kLdsBytes, stream, x, (f2 *) X, batch, (const f2 *) aux, in_pitch, in_len PROBE_NULL);
 }
 
 void dsc_launch_irfft64k(const void *X, float *x, int batch, int in_pitch, int in_len, const void *aux, int n_cu, hipStream_t stream) {
     if (batch <= 0) return;
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) irfft64k_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-    }
     const int grid = batch < n_cu ? batch : n_cu;
-    DSC_LAUNCH(irfft64k_kernel, dim3(grid), dim3(1024), kLdsBytes, stream, (const f2 *) X, x, batch, (const f2 *) aux, in_pitch, in_len PROBE_NULL);
+    dsc_launch_dyn_lds<irfft64k_kernel>(grid, 1024, kLdsBytes, stream, (const f2 *) X, x, batch, (const f2 *) aux, in_pitch, in_len PROBE_NULL);
 }
 void dsc_launch_filter64k(const float *s, const void *H, float *y, int batch, int in_pitch, int in_len, const void *aux, int n_cu,
                           hipStream_t stream) {
     if (batch <= 0) return;
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) filter64k_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes));
-    }
     const int grid = batch < n_cu ? batch : n_cu;
-    DSC_LAUNCH(filter64k_kernel, dim3(grid), dim3(1024), kLdsBytes, stream, s, (const f2 *) H, y, batch, (const f2 *) aux, in_pitch, in_len);
+    dsc_launch_dyn_lds<filter64k_kernel>(grid, 1024, kLdsBytes, stream, s, (const f2 *) H, y, batch, (const f2 *) aux, in_pitch, in_len);
 }
 #endif  // DSC_R2C64K_HELPERS_ONLY

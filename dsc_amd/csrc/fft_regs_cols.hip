@@ -15,7 +15,7 @@
 // with the packed-real pre / post pass (dsc_fft.h:194-228) through an LDS staging plane [k][c].  This replaces
 // transpose -> last-axis kernel -> transpose (three passes over HBM, 16-22 % of the roofline) and the strided LDS kernel for
 // complex lengths 32 .. 2048 (c32 data: 4096).
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -718,33 +718,6 @@ __global__ __launch_bounds__((cols_cfg<R, B, TWO, CW>::NT), (cols_cfg<R, B, TWO,
     (void) half;
 }
 
-template<typename R, int B, bool TWO, int CW>
-void launch_real_split(const void *work, void *out, long long slices, int cc_n, int n2, const void *tw_full, hipStream_t stream) {
-    using cfg = cols_cfg<R, B, TWO, CW>;
-    constexpr size_t lds = cols_lds_bytes<R, B, TWO, CW>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) cols_real_split_kernel<R, B, TWO, CW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const int tiles = (cc_n + CW / 2 - 1) / (CW / 2);
-    const long long grid = slices * (n2 / 2 + 1) * tiles;
-    DSC_LAUNCH((cols_real_split_kernel<R, B, TWO, CW>), dim3((unsigned) grid), dim3(cfg::NT), lds, stream, (const cpx<R> *) work, (cpx<R> *) out, cc_n,
-               tiles, n2, (const cpx<R> *) tw_full);
-}
-template<typename R, int B, bool TWO, int CW>
-void launch_real_merge(const void *in, void *work, long long slices, int cc_n, int n1, const void *tw_full, const void *twn, hipStream_t stream) {
-    using cfg = cols_cfg<R, B, TWO, CW>;
-    constexpr size_t lds = cols_lds_bytes<R, B, TWO, CW>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) cols_real_merge_kernel<R, B, TWO, CW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const int tiles = (cc_n + CW / 2 - 1) / (CW / 2);
-    const long long grid = slices * (n1 / 2 + 1) * tiles;
-    DSC_LAUNCH((cols_real_merge_kernel<R, B, TWO, CW>), dim3((unsigned) grid), dim3(cfg::NT), lds, stream, (const cpx<R> *) in, (cpx<R> *) work,
-               cc_n, n1, tiles, (const cpx<R> *) tw_full, (const cpx<R> *) twn);
-}
-
 #ifndef DSC_COLS_CW_64          // columns per tile of the f32 forms (A/B knobs, tools/build_file_variant.sh)
 #define DSC_COLS_CW_64 128
 #endif
@@ -766,39 +739,46 @@ void launch_real_merge(const void *in, void *work, long long slices, int cc_n, i
 #ifndef DSC_COLS_CW_4096
 #define DSC_COLS_CW_4096 8
 #endif
-template<typename R, int B, bool TWO, int CW, int MODE, bool INV>
-void launch_cols_one(const void *in, void *out, long long slices, int inner, int in_axis, int in_len, int out_axis, const void *tw_full,
-                     const void *tw_real, double scale, const cols_remap &rm, hipStream_t stream) {
-    using cfg = cols_cfg<R, B, TWO, CW>;
-    constexpr size_t lds = cols_lds_bytes<R, B, TWO, CW>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_cols_kernel<R, B, TWO, CW, MODE, INV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
+
+// Complex length -> (B, TWO, CW) of the column kernels: L = 32 B in two passes (TWO) or 1024 B in three, CW columns per tile.  The one
+// table of this file: the transforms, the real split / merge passes and the four-step split (cols_tile_width) all read it.  The f32
+// widths follow the knobs, so under a non-default DSC_COLS_CW_512 ... 2048 the split / merge kernels and the four-step split move
+// with the transforms (the knobs are A/B aids).  A length without a kernel ends the process.
+template<typename R, int MODE, typename F> void with_cols_len(int L, int_c<MODE>, F f) {
+    constexpr bool SP = sizeof(R) == 4;
+    switch (L) {
+        case 32:   return f(int_c<1>{}, bool_c<true>{}, int_c<256>{});
+        case 64:   return f(int_c<2>{}, bool_c<true>{}, int_c<SP ? DSC_COLS_CW_64 : 128>{});
+        case 128:  return f(int_c<4>{}, bool_c<true>{}, int_c<SP ? DSC_COLS_CW_128 : 64>{});
+        case 256:  return f(int_c<8>{}, bool_c<true>{}, int_c<SP ? DSC_COLS_CW_256 : 32>{});
+        case 512:  return f(int_c<16>{}, bool_c<true>{}, int_c<SP ? DSC_COLS_CW_512 : 16>{});
+        case 1024:                                      // real rows are 4 B per column: 32 columns make them whole 128-B lines
+            if constexpr (SP && MODE == DSC_MODE_R2C_PACKED) return f(int_c<32>{}, bool_c<true>{}, int_c<32>{});
+            else return f(int_c<32>{}, bool_c<true>{}, int_c<SP ? DSC_COLS_CW_1024 : 16>{});
+        case 2048: return f(int_c<2>{}, bool_c<false>{}, int_c<SP ? DSC_COLS_CW_2048 : 8>{});
+        case 4096:                                      // c32 data only, see dsc_fft_regs_cols_supports
+            if constexpr (SP && MODE == DSC_MODE_C2C) return f(int_c<4>{}, bool_c<false>{}, int_c<DSC_COLS_CW_4096>{});
+            else break;
     }
-    const int tiles = (inner + CW - 1) / CW;
-    const long long n_tiles = slices * tiles;
-    long long grid = n_tiles;
-    if (cfg::PIPE && !TWO) {                                // persistent: one workgroup per CU walks the tiles
-        static int cus[64];
-        int dev = 0;
-        DSC_KERNEL_CHECK(hipGetDevice(&dev));
-        dev &= 63;
-        if (cus[dev] == 0) DSC_KERNEL_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        if (grid > cus[dev]) grid = cus[dev];
-    }
-    DSC_LAUNCH((fft_cols_kernel<R, B, TWO, CW, MODE, INV>), dim3((unsigned) grid), dim3(cfg::NT), lds, stream, in, out, inner, tiles, (int) n_tiles,
-               in_axis, in_len, out_axis, (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) scale, rm);
+    no_kernel("fft_regs_cols.hip", "complex length", L);
 }
 
-template<typename R, int B, bool TWO, int CW>
-void launch_cols_mode(dsc_fft_mode mode, bool inverse, const void *in, void *out, long long slices, int inner, int in_axis, int in_len, int out_axis,
-                      const void *tw_full, const void *tw_real, double scale, const cols_remap &rm, hipStream_t stream) {
-    if (mode == DSC_MODE_R2C_PACKED)      launch_cols_one<R, B, TWO, CW, DSC_MODE_R2C_PACKED, false>(in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream);
-    else if (mode == DSC_MODE_C2R_PACKED) launch_cols_one<R, B, TWO, CW, DSC_MODE_C2R_PACKED, true>(in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream);
-    else if (mode == DSC_MODE_R2C_CAST && inverse) launch_cols_one<R, B, TWO, CW, DSC_MODE_R2C_CAST, true>(in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream);
-    else if (mode == DSC_MODE_R2C_CAST)   launch_cols_one<R, B, TWO, CW, DSC_MODE_R2C_CAST, false>(in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream);
-    else if (inverse)                     launch_cols_one<R, B, TWO, CW, DSC_MODE_C2C, true>(in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream);
-    else                                  launch_cols_one<R, B, TWO, CW, DSC_MODE_C2C, false>(in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream);
+// ... its CW alone, as the four-step split asks (complex data)
+int cols_tile_width(int L, bool single_precision) {
+    int width = 0;
+    with_real(single_precision, [&](auto real) {
+        with_cols_len<decltype(real)>(L, int_c<DSC_MODE_C2C>{}, [&](auto, auto, auto cw) { width = decltype(cw)::value; });
+    });
+    return width;
+}
+
+// ... for the real split / merge passes: complex columns, 64 .. 2048 points (no such kernel exists at 32 or 4096)
+template<typename R, typename F> void with_real_pass_len(int L, F f) {
+    with_cols_len<R>(L, int_c<DSC_MODE_C2C>{}, [&](auto b, auto two, auto cw) {
+        constexpr int LEN = (decltype(two)::value ? 32 : 1024) * decltype(b)::value;
+        if constexpr (LEN >= 64 && LEN <= 2048) f(b, two, cw);
+        else no_kernel("fft_regs_cols.hip", "real-pass complex length", L);
+    });
 }
 
 }  // namespace
@@ -817,33 +797,21 @@ static void launch_cols_len(const void *in, void *out, long long slices, int inn
                             const void *tw_full, const void *tw_real, double scale, int in_axis, int in_len, int out_axis, const cols_remap &rm,
                             hipStream_t stream) {
     if (slices <= 0 || inner <= 0) return;
-#define COLS_ARGS mode, inverse, in, out, slices, inner, in_axis, in_len, out_axis, tw_full, tw_real, scale, rm, stream
-    if (single_precision) {
-        switch (L) {
-            case 32:   launch_cols_mode<float, 1, true, 256>(COLS_ARGS); break;
-            case 64:   launch_cols_mode<float, 2, true, DSC_COLS_CW_64>(COLS_ARGS); break;
-            case 128:  launch_cols_mode<float, 4, true, DSC_COLS_CW_128>(COLS_ARGS); break;
-            case 256:  launch_cols_mode<float, 8, true, DSC_COLS_CW_256>(COLS_ARGS); break;
-            case 512:  launch_cols_mode<float, 16, true, DSC_COLS_CW_512>(COLS_ARGS); break;
-            case 1024:                                  // real rows are 4 B per column: 32 columns make them whole 128-B lines
-                if (mode == DSC_MODE_R2C_PACKED) launch_cols_mode<float, 32, true, 32>(COLS_ARGS);
-                else                             launch_cols_mode<float, 32, true, DSC_COLS_CW_1024>(COLS_ARGS);
-                break;
-            case 2048: launch_cols_mode<float, 2, false, DSC_COLS_CW_2048>(COLS_ARGS); break;
-            default:   launch_cols_mode<float, 4, false, DSC_COLS_CW_4096>(COLS_ARGS); break;
-        }
-    } else {
-        switch (L) {
-            case 32:   launch_cols_mode<double, 1, true, 256>(COLS_ARGS); break;
-            case 64:   launch_cols_mode<double, 2, true, 128>(COLS_ARGS); break;
-            case 128:  launch_cols_mode<double, 4, true, 64>(COLS_ARGS); break;
-            case 256:  launch_cols_mode<double, 8, true, 32>(COLS_ARGS); break;
-            case 512:  launch_cols_mode<double, 16, true, 16>(COLS_ARGS); break;
-            case 1024: launch_cols_mode<double, 32, true, 16>(COLS_ARGS); break;
-            default:   launch_cols_mode<double, 2, false, 8>(COLS_ARGS); break;
-        }
-    }
-#undef COLS_ARGS
+    with_real(single_precision, [&](auto real) { with_mode(mode, inverse, [&](auto m, auto inv) {
+        using R = decltype(real);
+        with_cols_len<R>(L, m, [&](auto b, auto two, auto cw) {
+            constexpr int B = decltype(b)::value, CW = decltype(cw)::value;
+            constexpr bool TWO = decltype(two)::value;
+            using cfg = cols_cfg<R, B, TWO, CW>;
+            const int tiles = (inner + CW - 1) / CW;
+            const long long n_tiles = slices * tiles;
+            long long grid = n_tiles;
+            if (cfg::PIPE && !TWO) grid = std::min<long long>(grid, dsc_cu_count());      // persistent: one workgroup per CU walks the tiles
+            dsc_launch_dyn_lds<fft_cols_kernel<R, B, TWO, CW, decltype(m)::value, decltype(inv)::value>>(
+                (unsigned) grid, cfg::NT, cols_lds_bytes<R, B, TWO, CW>(), stream, in, out, inner, tiles, (int) n_tiles, in_axis, in_len, out_axis,
+                (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) scale, rm);
+        });
+    }); });
 }
 
 void dsc_launch_fft_regs_cols(const void *in, void *out, long long slices, int inner, int L, dsc_fft_mode mode, bool inverse, bool single_precision,
@@ -860,15 +828,6 @@ void dsc_launch_fft_regs_cols(const void *in, void *out, long long slices, int i
 // Both passes move pieces of a whole tile row (32 - 128 columns); the route through two transposes and a row transform is three
 // passes.  mode: DSC_MODE_C2C or DSC_MODE_R2C_CAST (real input, widened while pass 1 loads).  work: slices n inner complex.
 // tw1 / tw2: W_{n1}^m / W_{n2}^m (the complex plans of the two lengths), twn: W_n^m, m < n.  The caller checks the 2 GiB slice limit.
-// columns per tile of the column kernel at complex length L (the table of launch_cols_len)
-static int cols_tile_width(int L, bool single_precision) {
-    if (L <= 32) return 256;
-    if (L == 64) return DSC_COLS_CW_64;
-    if (L == 128) return DSC_COLS_CW_128;
-    if (L == 256) return DSC_COLS_CW_256;
-    if (single_precision) return L == 512 ? DSC_COLS_CW_512 : L <= 2048 ? 16 : 8;
-    return L <= 1024 ? 16 : 8;
-}
 
 // n = n1 n2: balanced (n1 <= n2: the longer lines go to pass 1, whose tiles are always whole); when the tensor has fewer columns than a
 // pass-2 tile of n1-point lines is wide, bits move from n2 to n1 — longer lines have narrower tiles — as long as n2 stays >= 64
@@ -881,7 +840,7 @@ bool dsc_fft_cols_4step_split(int n, bool single_precision, int cols, int *n1, i
     static const int skew = [] { const char *e = getenv("DSC_COLS_4STEP_SKEW"); return e ? atoi(e) : 0; }();      // experiments: n1 >> skew
     for (int i = 0; i < skew && a > 64 && b < 2048; ++i) { a >>= 1; b <<= 1; }
     static const bool widen = getenv("DSC_COLS_4STEP_NO_WIDEN") == nullptr;
-    while (widen && cols_tile_width(a, single_precision) > cols && b >= 128 && a < 2048) { a <<= 1; b >>= 1; }
+    while (widen && a < 2048 && b >= 128 && cols_tile_width(a, single_precision) > cols) { a <<= 1; b >>= 1; }
     if (a < 32 || b < 32 || a > 2048 || b > 2048) return false;
     *n1 = a;
     *n2 = b;
@@ -890,43 +849,43 @@ bool dsc_fft_cols_4step_split(int n, bool single_precision, int cols, int *n1, i
 
 // Real transforms along the middle axis of [slices][n][2 cc_n] reals (see cols_real_split_kernel): cc_n = complex columns = half the real ones.
 // rfft: in = the real tensor, out = [slices][n/2 + 1][2 cc_n] complex.  irfft: the other way round, scale = 1 / n.  work: slices n cc_n complex.
-template<typename R>
-static void launch_real_split_len(int L, const void *work, void *out, long long slices, int cc_n, int n2, const void *tw, hipStream_t st) {
-    constexpr bool SP = sizeof(R) == 4;
-    switch (L) {
-        case 64:   launch_real_split<R, 2, true, 128>(work, out, slices, cc_n, n2, tw, st); break;
-        case 128:  launch_real_split<R, 4, true, 64>(work, out, slices, cc_n, n2, tw, st); break;
-        case 256:  launch_real_split<R, 8, true, 32>(work, out, slices, cc_n, n2, tw, st); break;
-        case 512:  launch_real_split<R, 16, true, SP ? 32 : 16>(work, out, slices, cc_n, n2, tw, st); break;
-        case 1024: launch_real_split<R, 32, true, 16>(work, out, slices, cc_n, n2, tw, st); break;
-        default:   launch_real_split<R, 2, false, SP ? 16 : 8>(work, out, slices, cc_n, n2, tw, st); break;
-    }
+// split: work [slices][n2][n1][cc_n] -> bins, lines of n1 points; merge: bins -> work, lines of n2 points
+static void launch_real_split(int n1, const void *work, void *out, long long slices, int cc_n, int n2, bool single_precision, const void *tw,
+                              hipStream_t stream) {
+    with_real(single_precision, [&](auto real) { with_real_pass_len<decltype(real)>(n1, [&](auto b, auto two, auto cw) {
+        using R = decltype(real);
+        constexpr int B = decltype(b)::value, CW = decltype(cw)::value;
+        constexpr bool TWO = decltype(two)::value;
+        const int tiles = (cc_n + CW / 2 - 1) / (CW / 2);
+        const long long grid = slices * (n2 / 2 + 1) * tiles;
+        dsc_launch_dyn_lds<cols_real_split_kernel<R, B, TWO, CW>>((unsigned) grid, cols_cfg<R, B, TWO, CW>::NT, cols_lds_bytes<R, B, TWO, CW>(), stream,
+                                                                  (const cpx<R> *) work, (cpx<R> *) out, cc_n, tiles, n2, (const cpx<R> *) tw);
+    }); });
 }
-template<typename R>
-static void launch_real_merge_len(int L, const void *in, void *work, long long slices, int cc_n, int n1, const void *tw, const void *twn, hipStream_t st) {
-    constexpr bool SP = sizeof(R) == 4;
-    switch (L) {
-        case 64:   launch_real_merge<R, 2, true, 128>(in, work, slices, cc_n, n1, tw, twn, st); break;
-        case 128:  launch_real_merge<R, 4, true, 64>(in, work, slices, cc_n, n1, tw, twn, st); break;
-        case 256:  launch_real_merge<R, 8, true, 32>(in, work, slices, cc_n, n1, tw, twn, st); break;
-        case 512:  launch_real_merge<R, 16, true, SP ? 32 : 16>(in, work, slices, cc_n, n1, tw, twn, st); break;
-        case 1024: launch_real_merge<R, 32, true, 16>(in, work, slices, cc_n, n1, tw, twn, st); break;
-        default:   launch_real_merge<R, 2, false, SP ? 16 : 8>(in, work, slices, cc_n, n1, tw, twn, st); break;
-    }
+static void launch_real_merge(int n2, const void *in, void *work, long long slices, int cc_n, int n1, bool single_precision, const void *tw,
+                              const void *twn, hipStream_t stream) {
+    with_real(single_precision, [&](auto real) { with_real_pass_len<decltype(real)>(n2, [&](auto b, auto two, auto cw) {
+        using R = decltype(real);
+        constexpr int B = decltype(b)::value, CW = decltype(cw)::value;
+        constexpr bool TWO = decltype(two)::value;
+        const int tiles = (cc_n + CW / 2 - 1) / (CW / 2);
+        const long long grid = slices * (n1 / 2 + 1) * tiles;
+        dsc_launch_dyn_lds<cols_real_merge_kernel<R, B, TWO, CW>>((unsigned) grid, cols_cfg<R, B, TWO, CW>::NT, cols_lds_bytes<R, B, TWO, CW>(), stream,
+                                                                  (const cpx<R> *) in, (cpx<R> *) work, cc_n, n1, tiles, (const cpx<R> *) tw,
+                                                                  (const cpx<R> *) twn);
+    }); });
 }
 
 void dsc_launch_rfft_cols_4step(const void *in, void *work, void *out, long long slices, int cc_n, int n1, int n2, bool single_precision,
                                 const void *tw1, const void *tw2, const void *twn, hipStream_t stream) {
     launch_cols_len(in, work, slices, n1 * cc_n, n2, DSC_MODE_C2C, false, single_precision, tw2, nullptr, 1.0, n2, n2, n2,
                     cols_remap{n1 * cc_n, 1, twn, cc_n}, stream);
-    if (single_precision) launch_real_split_len<float>(n1, work, out, slices, cc_n, n2, tw1, stream);
-    else                  launch_real_split_len<double>(n1, work, out, slices, cc_n, n2, tw1, stream);
+    launch_real_split(n1, work, out, slices, cc_n, n2, single_precision, tw1, stream);
 }
 
 void dsc_launch_irfft_cols_4step(const void *in, void *work, void *out, long long slices, int cc_n, int n1, int n2, bool single_precision,
                                  const void *tw1, const void *tw2, const void *twn, double scale, hipStream_t stream) {
-    if (single_precision) launch_real_merge_len<float>(n2, in, work, slices, cc_n, n1, tw2, twn, stream);
-    else                  launch_real_merge_len<double>(n2, in, work, slices, cc_n, n1, tw2, twn, stream);
+    launch_real_merge(n2, in, work, slices, cc_n, n1, single_precision, tw2, twn, stream);
     launch_cols_len(work, out, slices * n2, cc_n, n1, DSC_MODE_C2C, true, single_precision, tw1, nullptr, scale, n1, n1, n1,
                     cols_remap{n2 * cc_n, n2, nullptr, 1}, stream);
 }

@@ -20,11 +20,10 @@
 //
 // Reference: exec_fft / exec_rfft (dsc/src/dsc.cpp:1958-2007, 2102-2171) over
 // dsc_complex_fft / dsc_real_fft (dsc/include/dsc_fft.h:57-238).
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
 #include <utility>
 
 #include "fft_regs_common.h"
@@ -1126,28 +1125,9 @@ __global__ __launch_bounds__((small_cfg<R, MODE>::NT)) void fft_small_kernel(con
 }
 
 // ------------------------------------------------------------------------------------------------
-// Host side: from the run-time (precision, length, mode, direction) to the instantiation.  Each with_... hands its choice to a generic
-// callable as compile-time constants; a length without a kernel ends the process.
-template<int V> using int_c = std::integral_constant<int, V>;
-template<bool V> using bool_c = std::integral_constant<bool, V>;
-
-[[noreturn]] void no_kernel(const char *what, int L) {
-    fprintf(stderr, "fft_regs_mid.hip: no %s kernel for complex length %d\n", what, L);
-    exit(EXIT_FAILURE);
-}
-
-template<typename F> void with_real(bool single_precision, F f) { if (single_precision) f(float{}); else f(double{}); }
-template<typename F> void with_bool(bool b, F f) { if (b) f(bool_c<true>{}); else f(bool_c<false>{}); }
-
-// (mode, inverse) -> (MODE, INV): the packed-real modes have one direction each
-template<typename F> void with_mode(dsc_fft_mode mode, bool inverse, F f) {
-    switch (mode) {
-        case DSC_MODE_R2C_PACKED: return f(int_c<DSC_MODE_R2C_PACKED>{}, bool_c<false>{});
-        case DSC_MODE_C2R_PACKED: return f(int_c<DSC_MODE_C2R_PACKED>{}, bool_c<true>{});
-        case DSC_MODE_R2C_CAST:   return with_bool(inverse, [&](auto inv) { f(int_c<DSC_MODE_R2C_CAST>{}, inv); });
-        case DSC_MODE_C2C:        return with_bool(inverse, [&](auto inv) { f(int_c<DSC_MODE_C2C>{}, inv); });
-    }
-}
+// Host side: from the run-time (precision, length, mode, direction) to the instantiation with the tables of dispatch.h and the two
+// length tables below; a length without a kernel ends the process.
+[[noreturn]] void no_mid_kernel(const char *what, int L) { no_kernel("fft_regs_mid.hip", what, L); }
 
 // complex length -> (B, TWO) of fft_mid_kernel and fft_mid_filter_kernel (mid_cfg::L)
 template<typename F> void with_mid_len(int L, F f) {
@@ -1159,7 +1139,7 @@ template<typename F> void with_mid_len(int L, F f) {
         case 4096:  return f(int_c<4>{}, bool_c<false>{});
         case 8192:  return f(int_c<8>{}, bool_c<false>{});
         case 16384: return f(int_c<16>{}, bool_c<false>{});
-        default:    no_kernel("direct-load", L);
+        default:    no_mid_kernel("direct-load complex length", L);
     }
 }
 
@@ -1170,21 +1150,14 @@ template<typename F> void with_small_len(int L, F f) {
         case 64:  return f(int_c<2>{});
         case 128: return f(int_c<4>{});
         case 256: return f(int_c<8>{});
-        default:  no_kernel("LDS-staged", L);
+        default:  no_mid_kernel("LDS-staged complex length", L);
     }
 }
 
 // workgroups of G lines each; a persistent kernel (mid_cfg::PIPE) gets one per CU at the most and walks the lines
 unsigned groups_of(long long n_lines, int G, bool persistent = false) {
     long long groups = (n_lines + G - 1) / G;
-    if (persistent) {
-        static int cus[64];
-        int dev = 0;
-        DSC_KERNEL_CHECK(hipGetDevice(&dev));
-        dev &= 63;
-        if (cus[dev] == 0) DSC_KERNEL_CHECK(hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev));
-        if (groups > cus[dev]) groups = cus[dev];
-    }
+    if (persistent) groups = std::min<long long>(groups, dsc_cu_count());
     return (unsigned) groups;
 }
 
@@ -1199,7 +1172,7 @@ void launch_lines_len(int L, const void *in, void *out, long long n_lines, const
         constexpr int B = decltype(b)::value;
         constexpr bool TWO = decltype(two)::value;
         using cfg = mid_cfg<R, B, TWO>;
-        if constexpr (FRAMES && cfg::L == 256) no_kernel("direct-load stft", L);      // frames of 256 points: the LDS-staged kernel only
+        if constexpr (FRAMES && cfg::L == 256) no_mid_kernel("direct-load stft complex length", L);      // frames of 256 points: the LDS-staged kernel only
         else dsc_launch_dyn_lds<fft_mid_kernel<R, B, TWO, MODE, INV, PAD, SRC...>>(
                  groups_of(n_lines, cfg::G, cfg::PIPE && !FRAMES), cfg::NT, mid_lds_bytes<R, B, TWO>(), stream, (const C *) in, (C *) out, n_lines,
                  (const C *) tw_full, (const C *) tw_real, (R) scale, in_pitch_b, in_len_b, src...);
@@ -1213,7 +1186,7 @@ void launch_lines_len(int L, const void *in, void *out, long long n_lines, const
         });
     } else if (L == 32768) {                                                    // the one special length: f32 complex data only
         if constexpr (sizeof(R) == 4 && MODE == DSC_MODE_C2C && !FRAMES) mid(int_c<32>{}, bool_c<false>{});
-        else no_kernel("direct-load", L);
+        else no_mid_kernel("direct-load complex length", L);
     } else {
         with_mid_len(L, mid);
     }

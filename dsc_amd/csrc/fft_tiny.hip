@@ -8,7 +8,7 @@
 // Before: fft_lines_kernel (fft_generic.hip) at 20-45 % of the roofline for these lengths.
 //
 // Reference: exec_fft / exec_rfft (dsc/src/dsc.cpp:1958-2007, 2102-2171) over dsc_complex_fft / dsc_real_fft (dsc_fft.h:57-238).
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -206,69 +206,15 @@ __global__ __launch_bounds__(kTinyNT) void fft_tiny_cols_kernel(const void *__re
     }
 }
 
-template<typename R, int L, int MODE, bool INV>
-void launch_tiny_cols_one(const void *in, void *out, long long slices, int inner, int in_axis, int in_len, int out_axis, double scale, hipStream_t stream) {
-    const int tiles = (inner + kTinyNT - 1) / kTinyNT;
-    DSC_LAUNCH((fft_tiny_cols_kernel<R, L, MODE, INV>), dim3((unsigned) (slices * tiles)), dim3(kTinyNT), 0, stream, in, out, inner, tiles, in_axis, in_len,
-               out_axis, (R) scale);
-}
-template<typename R, int L>
-void launch_tiny_cols(const void *in, void *out, long long slices, int inner, int in_axis, int in_len, int out_axis, dsc_fft_mode mode, bool inverse,
-                      double scale, hipStream_t stream) {
-    if (mode == DSC_MODE_R2C_PACKED)      launch_tiny_cols_one<R, L, DSC_MODE_R2C_PACKED, false>(in, out, slices, inner, in_axis, in_len, out_axis, scale, stream);
-    else if (mode == DSC_MODE_C2R_PACKED) launch_tiny_cols_one<R, L, DSC_MODE_C2R_PACKED, true>(in, out, slices, inner, in_axis, in_len, out_axis, scale, stream);
-    else if (mode == DSC_MODE_R2C_CAST && !inverse) launch_tiny_cols_one<R, L, DSC_MODE_R2C_CAST, false>(in, out, slices, inner, in_axis, in_len, out_axis, scale, stream);
-    else if (mode == DSC_MODE_R2C_CAST)   launch_tiny_cols_one<R, L, DSC_MODE_R2C_CAST, true>(in, out, slices, inner, in_axis, in_len, out_axis, scale, stream);
-    else if (inverse)                     launch_tiny_cols_one<R, L, DSC_MODE_C2C, true>(in, out, slices, inner, in_axis, in_len, out_axis, scale, stream);
-    else                                  launch_tiny_cols_one<R, L, DSC_MODE_C2C, false>(in, out, slices, inner, in_axis, in_len, out_axis, scale, stream);
-}
-template<typename R>
-void launch_tiny_cols_len(int L, const void *in, void *out, long long slices, int inner, int in_axis, int in_len, int out_axis, dsc_fft_mode mode,
-                          bool inverse, double scale, hipStream_t stream) {
+// complex length -> L of fft_tiny_kernel / fft_tiny_cols_kernel; a length without a kernel ends the process
+template<typename F> void with_tiny_len(int L, F f) {
     switch (L) {
-        case 2:  launch_tiny_cols<R, 2>(in, out, slices, inner, in_axis, in_len, out_axis, mode, inverse, scale, stream); break;
-        case 4:  launch_tiny_cols<R, 4>(in, out, slices, inner, in_axis, in_len, out_axis, mode, inverse, scale, stream); break;
-        case 8:  launch_tiny_cols<R, 8>(in, out, slices, inner, in_axis, in_len, out_axis, mode, inverse, scale, stream); break;
-        default: launch_tiny_cols<R, 16>(in, out, slices, inner, in_axis, in_len, out_axis, mode, inverse, scale, stream); break;
+        case 2:  return f(int_c<2>{});
+        case 4:  return f(int_c<4>{});
+        case 8:  return f(int_c<8>{});
+        case 16: return f(int_c<16>{});
     }
-}
-
-template<typename R, int L, int MODE, bool INV, bool PAD>
-void launch_tiny_pad(const void *in, void *out, long long n_lines, double scale, int in_pitch_b, int in_len_b, hipStream_t stream) {
-    constexpr size_t lds = tiny_lds_bytes<R, L>();
-    static unsigned long long attr_devices = 0;
-    if (dsc_first_use_on_device(attr_devices)) {
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) fft_tiny_kernel<R, L, MODE, INV, PAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    }
-    const long long groups = (n_lines + kTinyNT - 1) / kTinyNT;
-    DSC_LAUNCH((fft_tiny_kernel<R, L, MODE, INV, PAD>), dim3((unsigned) groups), dim3(kTinyNT), lds, stream, in, out, n_lines, (R) scale, in_pitch_b, in_len_b);
-}
-
-template<typename R, int L, int MODE, bool INV>
-void launch_tiny_one(const void *in, void *out, long long n_lines, double scale, long long in_pitch_b, int in_len_b, hipStream_t stream) {
-    if (in_pitch_b < 0) launch_tiny_pad<R, L, MODE, INV, false>(in, out, n_lines, scale, 0, 0, stream);
-    else                launch_tiny_pad<R, L, MODE, INV, true>(in, out, n_lines, scale, (int) in_pitch_b, in_len_b, stream);
-}
-
-template<typename R, int L>
-void launch_tiny(const void *in, void *out, long long n_lines, dsc_fft_mode mode, bool inverse, double scale, long long pb, int lb, hipStream_t stream) {
-    if (mode == DSC_MODE_R2C_PACKED)      launch_tiny_one<R, L, DSC_MODE_R2C_PACKED, false>(in, out, n_lines, scale, pb, lb, stream);
-    else if (mode == DSC_MODE_C2R_PACKED) launch_tiny_one<R, L, DSC_MODE_C2R_PACKED, true>(in, out, n_lines, scale, pb, lb, stream);
-    else if (mode == DSC_MODE_R2C_CAST && !inverse) launch_tiny_one<R, L, DSC_MODE_R2C_CAST, false>(in, out, n_lines, scale, pb, lb, stream);
-    else if (mode == DSC_MODE_R2C_CAST)   launch_tiny_one<R, L, DSC_MODE_R2C_CAST, true>(in, out, n_lines, scale, pb, lb, stream);
-    else if (inverse)                     launch_tiny_one<R, L, DSC_MODE_C2C, true>(in, out, n_lines, scale, pb, lb, stream);
-    else                                  launch_tiny_one<R, L, DSC_MODE_C2C, false>(in, out, n_lines, scale, pb, lb, stream);
-}
-
-template<typename R>
-void launch_tiny_len(int L, const void *in, void *out, long long n_lines, dsc_fft_mode mode, bool inverse, double scale, long long pb, int lb,
-                     hipStream_t stream) {
-    switch (L) {
-        case 2:  launch_tiny<R, 2>(in, out, n_lines, mode, inverse, scale, pb, lb, stream); break;
-        case 4:  launch_tiny<R, 4>(in, out, n_lines, mode, inverse, scale, pb, lb, stream); break;
-        case 8:  launch_tiny<R, 8>(in, out, n_lines, mode, inverse, scale, pb, lb, stream); break;
-        default: launch_tiny<R, 16>(in, out, n_lines, mode, inverse, scale, pb, lb, stream); break;
-    }
+    no_kernel("fft_tiny.hip", "complex length", L);
 }
 
 }  // namespace
@@ -281,10 +227,17 @@ void dsc_launch_fft_tiny(const void *in, void *out, long long n_lines, int L, ds
                          long long in_pitch, int in_len, hipStream_t stream) {
     if (n_lines <= 0) return;
     const int eb = (single_precision ? 4 : 8) * ((mode == DSC_MODE_R2C_PACKED || mode == DSC_MODE_R2C_CAST) ? 1 : 2);
-    const long long pb = in_pitch < 0 ? -1 : in_pitch * eb;
-    const int lb = in_pitch < 0 ? 0 : in_len * eb;
-    if (single_precision) launch_tiny_len<float>(L, in, out, n_lines, mode, inverse, scale, pb, lb, stream);
-    else                  launch_tiny_len<double>(L, in, out, n_lines, mode, inverse, scale, pb, lb, stream);
+    const bool padded = in_pitch >= 0;
+    const int pb = padded ? (int) (in_pitch * eb) : 0, lb = padded ? in_len * eb : 0;      // the kernel counts bytes
+    const long long groups = (n_lines + kTinyNT - 1) / kTinyNT;
+    with_real(single_precision, [&](auto real) { with_tiny_len(L, [&](auto len) { with_mode(mode, inverse, [&](auto m, auto inv) {
+        with_bool(padded, [&](auto pad) {
+            using R = decltype(real);
+            constexpr int LEN = decltype(len)::value;
+            dsc_launch_dyn_lds<fft_tiny_kernel<R, LEN, decltype(m)::value, decltype(inv)::value, decltype(pad)::value>>(
+                (unsigned) groups, kTinyNT, tiny_lds_bytes<R, LEN>(), stream, in, out, n_lines, (R) scale, pb, lb);
+        });
+    }); }); });
 }
 
 // Tensor [slices][axis][inner] (contiguous), transform along `axis` (strided lines): in has in_axis elements along it of which in_len
@@ -292,6 +245,10 @@ void dsc_launch_fft_tiny(const void *in, void *out, long long n_lines, int L, ds
 void dsc_launch_fft_tiny_cols(const void *in, void *out, long long slices, int inner, int L, dsc_fft_mode mode, bool inverse, bool single_precision,
                               double scale, int in_axis, int in_len, int out_axis, hipStream_t stream) {
     if (slices <= 0 || inner <= 0) return;
-    if (single_precision) launch_tiny_cols_len<float>(L, in, out, slices, inner, in_axis, in_len, out_axis, mode, inverse, scale, stream);
-    else                  launch_tiny_cols_len<double>(L, in, out, slices, inner, in_axis, in_len, out_axis, mode, inverse, scale, stream);
+    const int tiles = (inner + kTinyNT - 1) / kTinyNT;
+    with_real(single_precision, [&](auto real) { with_tiny_len(L, [&](auto len) { with_mode(mode, inverse, [&](auto m, auto inv) {
+        using R = decltype(real);
+        DSC_LAUNCH((fft_tiny_cols_kernel<R, decltype(len)::value, decltype(m)::value, decltype(inv)::value>), dim3((unsigned) (slices * tiles)),
+                   dim3(kTinyNT), 0, stream, in, out, inner, tiles, in_axis, in_len, out_axis, (R) scale);
+    }); }); });
 }

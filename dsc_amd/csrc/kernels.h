@@ -35,16 +35,6 @@ static inline bool dsc_first_use_on_device(unsigned long long &seen) {
     return true;
 }
 
-// Launch of a kernel that takes `lds` bytes of dynamic LDS, the same size at every launch: opts the kernel in to that size the first
-// time it runs on the current device, then launches and checks.  The "seen on this device" state is per kernel.
-template<auto Kernel, typename... Args>
-static inline void dsc_launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args) {
-    static unsigned long long seen = 0;
-    if (dsc_first_use_on_device(seen))
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
-    DSC_LAUNCH(Kernel, grid, block, lds, stream, args...);
-}
-
 // A batch of 1-D lines inside a tensor.  Line q (0 <= q < n_lines) starts at element
 //   (q / inner) * outer_stride + (q % inner) * inner_stride
 // and advances by elem_stride per sample.  Strides are in elements of the array's own

@@ -33,7 +33,7 @@
 //
 // Padding taps are zeros that meet real samples just outside the filter's support: a non-finite sample spreads that much further than
 // in an exact sum.  No atomics, every output written once, accumulation in a fixed order in the data's type: results are deterministic.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -238,19 +238,14 @@ __global__ __launch_bounds__(kThreads) void polyphase_kernel(const poly_args a) 
 constexpr size_t kLdsMax = (size_t) 160 << 10;            // the LDS of a CU: the most one workgroup can take
 constexpr size_t kLdsTwo = kLdsMax / 2;                   // two workgroups per CU
 
-// the LDS size differs from launch to launch: the kernel is opted in to the whole 160 KiB once per device
-template<auto Kernel>
-void launch_one(const poly_args &a, unsigned grid, size_t lds, hipStream_t stream) {
-    static unsigned long long seen = 0;
-    if (dsc_first_use_on_device(seen))
-        DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) kLdsMax));
-    DSC_LAUNCH(Kernel, dim3(grid), dim3((a.S + 63) / 64 * 64), lds, stream, a);
-}
-
-template<typename R, int RB>
-void launch_rb(const poly_args &a, unsigned grid, size_t lds, hipStream_t stream) {
-    if (a.up == 1) launch_one<polyphase_kernel<R, RB, true>>(a, grid, lds, stream);
-    else           launch_one<polyphase_kernel<R, RB, false>>(a, grid, lds, stream);
+// outputs per thread -> RB of polyphase_kernel; another count ends the process
+template<typename F> void with_poly_rb(int RB, F f) {
+    switch (RB) {
+        case 1: return f(int_c<1>{});
+        case 2: return f(int_c<2>{});
+        case 4: return f(int_c<4>{});
+    }
+    no_kernel("polyphase.hip", "outputs per thread", RB);
 }
 
 // LDS bytes of a tile of S * RB outputs; fills the tile fields of a.  0 = the sizes do not fit an int
@@ -323,14 +318,9 @@ bool dsc_launch_polyphase(const void *x, const void *h, void *y, long long rows,
         exit(EXIT_FAILURE);
     }
     const unsigned grid = (unsigned) blocks;
-    if (single_precision) {
-        if (RB == 4) launch_rb<float, 4>(a, grid, lds, stream);
-        else if (RB == 2) launch_rb<float, 2>(a, grid, lds, stream);
-        else launch_rb<float, 1>(a, grid, lds, stream);
-    } else {
-        if (RB == 4) launch_rb<double, 4>(a, grid, lds, stream);
-        else if (RB == 2) launch_rb<double, 2>(a, grid, lds, stream);
-        else launch_rb<double, 1>(a, grid, lds, stream);
-    }
+    // the LDS size differs from launch to launch: the kernel is opted in to the whole 160 KiB
+    with_real(single_precision, [&](auto real) { with_poly_rb(RB, [&](auto rb) { with_bool(up == 1, [&](auto up1) {
+        dsc_launch_var_lds<polyphase_kernel<decltype(real), decltype(rb)::value, decltype(up1)::value>, kLdsMax>(grid, (a.S + 63) / 64 * 64, lds, stream, a);
+    }); }); });
     return true;
 }

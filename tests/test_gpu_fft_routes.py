@@ -335,6 +335,12 @@ def _four_step_cases():
         for L, inner in ((8192, 16), (65536, 8)):
             for kind in KINDS:
                 cases.append((kind, in_dtypes(kind, rdt)[0], L, inner, 'padded'))
+    # the 1024- and 2048-point rows of the column tables, at the smallest shapes that reach them: 2^21 real points = 1024 x 2048 (split at
+    # 1024, merge at 2048, column passes at both), and 2^21 complex points in eight columns, which widen the split to 2048 x 1024
+    for kind in ('rfft', 'irfft'):
+        cases.append((kind, in_dtypes(kind, F32)[0], 1 << 20, 16, 'full'))
+    for kind in ('fft', 'ifft'):
+        cases.append((kind, C128, 1 << 21, 8, 'full'))
     return cases
 
 

@@ -9,6 +9,7 @@ T=$(mktemp -d)
 if [ -n "$SRC_REF" ]; then git -C $ROOT archive $SRC_REF dsc_amd/csrc include | tar -x -C $T
 else mkdir -p $T/dsc_amd $T/include; cp -r $ROOT/dsc_amd/csrc $T/dsc_amd/csrc; cp $ROOT/include/*.h $T/include/; fi
 rm -rf $T/dsc_amd/csrc/build
+mkdir -p $ROOT/tools/bin
 sed -i "s|^OUT .*|OUT = $ROOT/tools/bin/lib$NAME.so|" $T/dsc_amd/csrc/Makefile
 sed -i "s|^\(FLAGS_[a-z0-9_]* = .*\)$|\1 $EXTRA|" $T/dsc_amd/csrc/Makefile
 make -s -j8 -C $T/dsc_amd/csrc 2>&1 | grep -E "error|\*\*\*" -A3 || true

@@ -1,6 +1,6 @@
 """dsc_rfft / dsc_irfft along a non-last axis at lengths that take the real four-step route (cols_4step_real: two columns as one complex
 column): every element against numpy (f64), f32 / f64, 2-D and 3-D, column counts that leave the last tile ragged, the imaginary
-parts of bins 0 and n/2 ignored by irfft.   usage: python tools/check_cols_4step_real.py [--bench]"""
+parts of bins 0 and n/2 ignored by irfft.   usage: python tools/check_cols_4step_real.py [--bench] [n=<N>: that length in 16 columns only]"""
 import sys
 sys.path.insert(0, '.')
 import numpy as np
@@ -11,9 +11,13 @@ from dsc_amd.context import _get_ctx
 dsc.init(12 << 30, 2 << 30)
 ctx = _get_ctx()
 rng = np.random.default_rng(11)
+SHAPES = (((8192, 40), 0), ((16384, 34), 0), ((3, 32768, 18), 1), ((65536, 24), 0), ((2, 131072, 16), 1), ((262144, 22), 0))
+for arg in sys.argv[1:]:
+    if arg.startswith('n='):
+        SHAPES = (((int(arg[2:]), 16), 0),)
 bad = 0
 for dt, tol in ((np.float32, 2e-6), (np.float64, 1e-13)):
-    for shape, axis in (((8192, 40), 0), ((16384, 34), 0), ((3, 32768, 18), 1), ((65536, 24), 0), ((2, 131072, 16), 1), ((262144, 22), 0)):
+    for shape, axis in SHAPES:
         x = rng.standard_normal(shape).astype(dt)
         got = dsc.rfft(dsc.from_numpy(x), axis=axis)
         path = dsc.last_fft_path()

@@ -1,0 +1,105 @@
+#!/usr/bin/env python3
+"""One small call per entry of the kernel files' dispatch tables, and the comparison of two builds' kernel traces of it.
+
+  rocprofv3 --kernel-trace --output-format csv -d DIR -- python3 tools/launch_census.py --run > DIR/paths.txt     (once per build, DSC_MI355X_LIB)
+  python3 tools/launch_census.py --compare DIR_A DIR_B
+
+--run     every complex length 1 .. 2^21 x rfft / irfft / fft / ifft (real and complex input) x f32 / f64 x full / zero-padded lines, on the
+          last axis (2 rows from 65536 points up) and, up to 2^16, on axis 0 with 70 columns; long axis-0 lines in 16 real / 8 complex
+          columns (the four-step passes at every length of the column table); every fft2 / rfft2 window; decimate / resample_poly shapes
+          for each polyphase tile form.  DSC_NO_FUSED_L2=1: rows of 65536 and 131072 points reach the two-pass launcher.  Prints one
+          line per call, 'CALL ... <dsc.last_fft_path()>'.
+--compare the kernel-trace CSVs below the two directories in dispatch order: the same sequence of (Kernel_Name, Grid_Size, Workgroup_Size,
+          LDS_Block_Size), and the same paths.txt.  Exits 1 on a difference.
+"""
+import csv
+import glob
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def run():
+    os.environ['DSC_NO_FUSED_L2'] = '1'
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import dsc_amd as dsc
+    dsc.init(10 << 30, 2 << 30)
+    F32, F64, C64, C128 = np.float32, np.float64, np.complex64, np.complex128
+    cpx = {F32: C64, F64: C128}
+
+    def call(what, fn, shape, dt, **kw):
+        x = dsc.from_numpy(np.ones(shape, dtype=dt))
+        y = fn(x, **kw)
+        print('CALL', what, np.dtype(dt).name, shape, kw, dsc.last_fft_path(), flush=True)
+        del x, y
+
+    def transforms(L, shape_of, axis, rdt):
+        # (kind, input dtype, full input length, padded input length and its n) as tests/test_gpu_fft_routes.py::fits
+        for kind, dt, full, short, n in (('rfft', rdt, 2 * L, max(1, 2 * L - 3), 2 * L), ('irfft', cpx[rdt], L + 1, max(2, L // 2 + 1), L + 1),
+                                         ('fft', cpx[rdt], L, max(1, L - 3), L), ('fft', rdt, L, max(1, L - 3), L),
+                                         ('ifft', cpx[rdt], L, max(1, L - 3), L), ('ifft', rdt, L, max(1, L - 3), L)):
+            call(kind, getattr(dsc, kind), shape_of(full), dt, axis=axis)
+            call(kind, getattr(dsc, kind), shape_of(short), dt, n=n, axis=axis)
+
+    for rdt in (F32, F64):
+        for lg in range(0, 22):                                     # 1 and 2^21: the generic LDS and four-step kernels
+            L = 1 << lg
+            transforms(L, lambda m: (2 if L >= 32768 else 3, m), -1, rdt)
+            if lg <= 16:
+                transforms(L, lambda m: (m, 70), 0, rdt)
+        for lg in range(12, 22):                                    # real four-step: n = 2^(lg + 1) = n1 n2, split at n1, merge at n2
+            call('rfft', dsc.rfft, (2 << lg, 16), rdt, axis=0)
+            call('irfft', dsc.irfft, ((1 << lg) + 1, 16), cpx[rdt], axis=0)
+        for lg in range(17, 22):                                    # complex four-step, eight columns: the widened split
+            call('fft', dsc.fft, (1 << lg, 8), cpx[rdt], axis=0)
+            call('ifft', dsc.ifft, (1 << lg, 8), cpx[rdt], axis=0)
+        for n0 in (32, 64, 128):
+            for n1 in (32, 64, 128):
+                for dt in (cpx[rdt], rdt):
+                    call('fft2', dsc.fft2, (2, n0, n1), dt)
+                    call('ifft2', dsc.ifft2, (2, n0 - 3, n1 - 1), dt, s=(n0, n1))
+                call('rfft2', dsc.rfft2, (2, n0, 2 * n1), rdt)
+        for T in (300, 900, 4096):                                  # 1, 2 and 4 outputs per thread
+            call('decimate', lambda x: dsc.decimate(x, 2), (2, T), rdt)
+        for T in (100, 260, 4096):
+            call('resample_poly', lambda x: dsc.resample_poly(x, 3, 2), (2, T), rdt)
+    dsc.synchronize()
+
+
+def trace(d):
+    files = sorted(glob.glob(os.path.join(d, '**', '*kernel_trace.csv'), recursive=True))
+    if len(files) != 1:
+        sys.exit('%s: %d kernel-trace files, expected one' % (d, len(files)))
+    rows = list(csv.DictReader(open(files[0])))
+    rows.sort(key=lambda r: int(r['Dispatch_Id']))
+
+    def size(r, name):
+        if name in r:
+            return int(r[name])
+        return int(r[name + '_X']) * int(r[name + '_Y']) * int(r[name + '_Z'])
+    return [(r['Kernel_Name'], size(r, 'Grid_Size'), size(r, 'Workgroup_Size'), int(r['LDS_Block_Size'])) for r in rows]
+
+
+def compare(a, b):
+    ta, tb = trace(a), trace(b)
+    diffs = [(i, x, y) for i, (x, y) in enumerate(zip(ta, tb)) if x != y]
+    for i, x, y in diffs[:20]:
+        print('dispatch %d:\n  A %s\n  B %s' % (i, x, y))
+    pa, pb = ([ln for ln in open(os.path.join(d, 'paths.txt')) if ln.startswith('CALL ')] for d in (a, b))
+    path_diffs = [(x, y) for x, y in zip(pa, pb) if x != y]
+    for x, y in path_diffs[:20]:
+        print('path:\n  A %s  B %s' % (x, y))
+    print('dispatches: %d in A, %d in B, %d differing; %d distinct kernels; calls: %d in A, %d in B, %d differing' % (
+        len(ta), len(tb), len(diffs), len({t[0] for t in ta}), len(pa), len(pb), len(path_diffs)))
+    sys.exit(1 if diffs or path_diffs or len(ta) != len(tb) or len(pa) != len(pb) else 0)
+
+
+if __name__ == '__main__':
+    if sys.argv[1:] == ['--run']:
+        run()
+    elif len(sys.argv) == 4 and sys.argv[1] == '--compare':
+        compare(sys.argv[2], sys.argv[3])
+    else:
+        sys.exit(__doc__)
