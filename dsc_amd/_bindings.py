@@ -183,6 +183,10 @@ dsc_resample_poly = _sig('dsc_resample_poly', _DscTensor_p, _DscCtx, _DscTensor_
 dsc_decimate = _sig('dsc_decimate', _DscTensor_p, _DscCtx, _DscTensor_p, c_int, c_int, _DscTensor_p)
 dsc_firwin = _sig('dsc_firwin', _DscTensor_p, _DscCtx, c_int, c_double, c_int, c_double, c_uint8)
 dsc_firwin_host = _sig('dsc_firwin_host', None, POINTER(c_double), c_int, c_double, c_int, c_double)
+dsc_cumsum = _sig('dsc_cumsum', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
+dsc_diff = _sig('dsc_diff', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
+dsc_unwrap = _sig('dsc_unwrap', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
+dsc_phase = _sig('dsc_phase', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope` and `dsc::upfirdn / resample_poly / decimate / firwin`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope`, `dsc::upfirdn / resample_poly / decimate / firwin` and `dsc::cumsum / diff / unwrap / phase`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -278,6 +278,17 @@ template<typename T>
 static inline tensor<T> decimate(const tensor<T> &x, int q, int n = 0) noexcept { return dsc_decimate(ctx, x.x_, q, n, nullptr); }
 template<typename T>
 static inline tensor<T> firwin(int numtaps, double cutoff, int window = 0, double beta = 5.0) noexcept { return dsc_firwin(ctx, numtaps, cutoff, window, beta, dtype_of<T>::value); }
+
+// Section I of dsc_mi355x.h: prefix scans along one axis (numpy.cumsum / diff / unwrap) and phase(z) = unwrap(angle(z)) in one pass
+// (a complex payload in, a real one out)
+template<typename T>
+static inline tensor<T> cumsum(const tensor<T> &x, int axis = -1) noexcept { return dsc_cumsum(ctx, x.x_, nullptr, axis); }
+template<typename T>
+static inline tensor<T> diff(const tensor<T> &x, int axis = -1) noexcept { return dsc_diff(ctx, x.x_, nullptr, axis); }
+template<typename T>
+static inline tensor<T> unwrap(const tensor<T> &x, int axis = -1) noexcept { return dsc_unwrap(ctx, x.x_, nullptr, axis); }
+template<typename T>
+static inline tensor<T> phase(const tensor<T> &z, int axis = -1) noexcept { return dsc_phase(ctx, z.x_, nullptr, axis); }
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

@@ -274,6 +274,20 @@ bool dsc_launch_binary_mixed(const void *a, int a_dtype, const void *b, int b_dt
 void dsc_launch_reduce(const void *x, void *out, int dtype, int op, long long outer, int axis_n, long long inner,
                        void *workspace, size_t workspace_bytes, hipStream_t stream);
 
+// ---- prefix scans along one axis (dsc_cumsum / dsc_diff / dsc_unwrap / dsc_phase, scan.cpp) ------
+// x viewed as [outer][n][inner] contiguous (scan.hip).  op: 0 cumsum (dtype f32 / f64 / c32 / c64, out of the same dtype), 1 unwrap
+// (f32 / f64, out of the same dtype), 2 phase (c32 / c64 in, f32 / f64 out); dtype is x's.  out has x's shape and must not overlap x.
+// rows / tiles: inner == 1, x = [rows][n].  rows: one launch, a workgroup per row.  tiles: three launches (tile totals, their scan per
+// row, the tiles with their carry-in) and dsc_scan_tiles_scratch_bytes() bytes of scratch, 256-byte aligned; a tile is
+// dsc_scan_tile_len() elements.  cols: any inner, one thread per (outer, inner) element.
+int    dsc_scan_tile_len(int op, int dtype);
+size_t dsc_scan_tiles_scratch_bytes(int op, int dtype, long long rows, int n);
+void   dsc_launch_scan_rows(const void *x, void *out, int op, int dtype, long long rows, int n, hipStream_t stream);
+void   dsc_launch_scan_tiles(const void *x, void *out, int op, int dtype, long long rows, int n, void *scratch, hipStream_t stream);
+void   dsc_launch_scan_cols(const void *x, void *out, int op, int dtype, long long outer, int n, long long inner, hipStream_t stream);
+// out [outer][n - 1][inner] = x[.][j + 1][.] - x[.][j][.], n >= 2, fewer than 2^31 output elements
+void   dsc_launch_scan_diff(const void *x, void *out, int dtype, long long outer, int n, long long inner, hipStream_t stream);
+
 // ---- strided gather / scatter of a slice region (indexing.cpp) -----------------------------
 // Region of a tensor: element (i0, i1, i2, i3), i_d < count[d], sits at base + sum_d i_d * stride[d]
 // (elements; strides may be negative).  Row-major order over the region = flat index of the dense side.

@@ -437,6 +437,31 @@ def envelope(x: Tensor, n: Union[int, None] = -1, out: Union[Tensor, None] = Non
     return _hilbert_like(B.dsc_envelope, x, n, out)
 
 
+# ---- prefix scans along one axis (include/dsc_mi355x.h, Section I): numpy.cumsum / diff / unwrap, and phase = unwrap(angle(z)) fused
+def _scan(f, x: Tensor, axis, out) -> Tensor:
+    return Tensor(f(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), int(axis)), out is not None)
+
+
+def cumsum(x: Tensor, axis: int = -1, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.cumsum(x, axis), accumulated in x's dtype (complex component-wise)."""
+    return _scan(B.dsc_cumsum, x, axis, out)
+
+
+def diff(x: Tensor, axis: int = -1, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.diff(x, 1, axis): out[j] = x[j + 1] - x[j]; the axis shrinks by one."""
+    return _scan(B.dsc_diff, x, axis, out)
+
+
+def unwrap(x: Tensor, axis: int = -1, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.unwrap(x, axis=axis) for real x: x - 2 pi K with K the exact integer scan of the whole periods between neighbours."""
+    return _scan(B.dsc_unwrap, x, axis, out)
+
+
+def phase(z: Tensor, axis: int = -1, out: Union[Tensor, None] = None) -> Tensor:
+    """unwrap(angle(z), axis) of complex z in one pass: real, bit-identical to the composition."""
+    return _scan(B.dsc_phase, z, axis, out)
+
+
 # ---- polyphase FIR resampling along the last axis (include/dsc_mi355x.h, Section H): scipy.signal.upfirdn / resample_poly / decimate
 # (ftype='fir') and the low-pass firwin, in one pass of the direct kernel; nothing is rounded to a power of two
 

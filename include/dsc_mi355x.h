@@ -383,6 +383,46 @@ dsc_tensor *dsc_firwin       (dsc_ctx *ctx, int numtaps, double cutoff, int wind
 void        dsc_firwin_host  (double *taps, int numtaps, double cutoff, int window, double beta);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section I — prefix scans along one axis (no reference counterpart).
+ *
+ * Along `axis` of x (any axis, negative counts from the end; at most 4 dims), the tensor viewed as [outer][n][inner] like the
+ * reductions.
+ *   dsc_cumsum(x, axis)   numpy.cumsum(x, axis): f32 / f64 / c32 / c64 (complex component-wise), shape and dtype unchanged.  Accumulated
+ *                         in x's dtype; no atomics, every output written once: bit-identical from run to run for a given shape and
+ *                         route.  Element 0 along the axis is a bit-for-bit copy.
+ *   dsc_diff(x, axis)     numpy.diff(x, 1, axis): out[j] = x[j + 1] - x[j], the four dtypes, the axis one shorter (n >= 2); one
+ *                         subtraction per component, equal to numpy bit for bit.
+ *   dsc_unwrap(x, axis)   numpy.unwrap(x, axis=axis), period 2 pi, default discontinuity, f32 / f64 — defined so that the result does
+ *                         not depend on the order of the scan.  With TWO_PI = 6.283185307179586 and PI = 3.141592653589793 as doubles:
+ *                           d[j] = (double) x[j] - (double) x[j - 1]                               j >= 1
+ *                           m[j] = 0 when |d[j]| <= PI or d[j] is not finite, else the integer nearest to d[j] / TWO_PI, ties toward zero
+ *                           K[j] = m[1] + .. + m[j], exact int32 arithmetic, K[0] = 0
+ *                           out[j] = x[j] - K[j] TWO_PI, formed in double (one FMA) and rounded once to x's dtype; K[j] = 0: a copy
+ *                         Every route gives the same bits; out[0] is a copy; rows without a jump come back unchanged.  Limits: |K| must
+ *                         stay below 2^31; a sample that is not finite does not spread to the samples after it (numpy's float cumsum of
+ *                         corrections would make them all NaN).  The definition agrees with numpy.unwrap in double to 6e-11 on rows of
+ *                         70001 samples with |K| up to 620 (numpy's own accumulated rounding; tests/test_scan_abi.py).
+ *   dsc_phase(z, axis)    dsc_unwrap(dsc_angle(z), axis) for z c32 / c64 in one pass, real result of the matching precision, bit-identical
+ *                         to the composition: the atan2 of dsc_angle in the load, the integer scan, one store.
+ * out: NULL or a tensor of the result's shape and dtype; it must not share memory with the input.  Argument errors (a wrong dtype, a
+ * wrong out, an overlap, an axis out of range, n < 2 for dsc_diff) print and exit like every operator.
+ * dsc_last_fft_path:
+ *   "scan_rows"   inner == 1, 128 rows or more (or rows of at most one tile of 2048 - 8192 elements): one workgroup walks a row in chunks and carries the running
+ *                 value in a register; persistent grid over the rows; one HBM round trip.
+ *   "scan_tiles"  inner == 1, fewer than 128 rows longer than a tile: three plain launches — per-tile totals into scratch, a scan of the totals per row, the tile
+ *                 scan with its carry-in.  x is read twice (ceiling: 2/3 of the roofline); no workgroup ever waits on another.
+ *   "scan_cols"   inner > 1: one thread per (outer, inner) element walks the axis sequentially, neighbouring threads on neighbouring
+ *                 addresses; dsc_cumsum is numpy's own left-to-right order here (bit-identical to numpy.cumsum).  The axis is not
+ *                 segmented: a few columns with a long axis are slow.
+ *   "scan_diff"   dsc_diff: element-wise.
+ * DSC_SCAN_ROUTE=rows|tiles (read at every call) forces either route on any inner == 1 shape.
+ */
+dsc_tensor *dsc_cumsum(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis);
+dsc_tensor *dsc_diff  (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis);
+dsc_tensor *dsc_unwrap(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis);
+dsc_tensor *dsc_phase (dsc_ctx *ctx, const dsc_tensor *z, dsc_tensor *out, int axis);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
