@@ -16,13 +16,10 @@
 //                  samples scattered to out (fft_conv.hip).
 #include "dsc_internal.h"
 #include "kernels.h"
-
-#include <cstdlib>
-#include <cstring>
+#include "op_common.h"
 
 namespace {
 
-constexpr size_t kChunkCapBytes = (size_t) 128 << 20;     // blocks per scratch chunk (frames + filtered frames): at most this many bytes
 constexpr int kFusedMaxN = 32768;
 
 int ilog2(long long n) {
@@ -88,70 +85,50 @@ dsc_tensor *conv_impl(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h, in
     int out_shape[DSC_MAX_DIMS];
     memcpy(out_shape, x->shape, sizeof(out_shape));
     out_shape[DSC_MAX_DIMS - 1] = (int) T_out;
-    if (out == nullptr) {
-        out = dsc_new_tensor(ctx, x->n_dim, &out_shape[DSC_MAX_DIMS - x->n_dim], x->dtype, nullptr);
-    } else {
-        if (out->dtype != x->dtype || out->n_dim != x->n_dim || memcmp(out_shape, out->shape, sizeof(out_shape)) != 0)
-            DSC_LOG_FATAL("out must have the input's dtype and shape [.., %lld]", T_out);
-        const char *xa = (const char *) x->data, *oa = (const char *) out->data;
-        if (oa < xa + (size_t) x->ne * rb && xa < oa + (size_t) out->ne * rb) DSC_LOG_FATAL("out must not share memory with x");
-    }
+    DSC_RESULT(out, ctx, x->n_dim, out_shape, x->dtype, "the input's dtype and shape [.., %lld]", T_out);
+    DSC_NO_OVERLAP(out, x, "x");
     if (rows == 0) return out;
 
     const int D = (M - 1) + ((M - 1) & 1);
     const int pad = D - (int) n0;                                  // block b starts at b hop - pad
     // fused: rows per launch such that every byte offset into x (one spare row, plus a block past its end) and into out fits 31 bits
-    const bool fused_off = getenv("DSC_NO_CONV_FUSED") != nullptr;     // read at every call: tools/bench_conv.py interleaves the routes
-    const long long lim = 0x7f000000LL - (long long) kFusedMaxN * (long long) rb;
-    const long long rows_per_x = lim / ((long long) T * (long long) rb) - 1, rows_per_y = lim / (T_out * (long long) rb) - 1;
-    // An even number of rows per launch keeps every launch's first element even, so that pairs the kernel finds aligned relative to
-    // its base are aligned in memory too; with odd rows a row too long for two per launch takes the composed route.
-    long long rows_per = rows_per_x < rows_per_y ? rows_per_x : rows_per_y;
-    if (rows_per > 1) rows_per &= ~1LL;
-    const bool launch_aligned = rows_per != 1 || rows == 1 || ((T | T_out) & 1) == 0;
-    const bool fused = !fused_off && D <= kFusedMaxN / 2 && rows_per >= 1 && launch_aligned;
+    const long long rows_per = dsc_fused_rows_per_launch(0x7f000000LL - (long long) kFusedMaxN * (long long) rb, (long long) T * (long long) rb,
+                                                         T_out * (long long) rb, rows, (T | T_out) & 1);
+    const bool fused = !dsc_env_set("DSC_NO_CONV_FUSED") && D <= kFusedMaxN / 2 && rows_per > 0;
     const int n = block_n(D, T_out, D <= kFusedMaxN / 2 ? kFusedMaxN : 1 << 20, !sp);
     const int hop = n - D;
     const long long n_blocks = (T_out + hop - 1) / hop;
     const int bins = n / 2 + 1;
 
     // H = rfft(h, n) (h reversed for correlate) in a pinned scratch block, with the composed route's two chunks next to it
-    ctx->scratch.reset();
-    char *Hb = ctx->scratch.alloc((size_t) bins * csz);
-    char *hr = reverse ? ctx->scratch.alloc((size_t) M * rb) : nullptr;
+    dsc_scratch_pin held(ctx);
+    const size_t capacity = ctx->scratch.capacity();
+    char *Hb = held.alloc((size_t) bins * csz);
+    char *hr = reverse ? held.alloc((size_t) M * rb) : nullptr;
     const size_t frame_b = (size_t) n * rb;
     long long chunk = 0;
     char *frames = nullptr, *filtered = nullptr;
     const long long n_lines = rows * n_blocks;
     if (!fused) {
-        // two blocks per chunk line (frames, filtered frames): half the arena, at most kChunkCapBytes, leaving the inner routes
-        // room for two more frames
-        const size_t cap = ctx->scratch.capacity() - ((size_t) bins * csz + (reverse ? (size_t) M * rb : 0) + 2 * DSC_DEVICE_ALIGN);
+        // two blocks per chunk line (frames, filtered frames) next to H and the reversed taps; the inner routes keep two more frames
+        const size_t fixed = (size_t) bins * csz + (reverse ? (size_t) M * rb : 0) + 2 * DSC_DEVICE_ALIGN;
         const size_t reserve = 2 * frame_b + 4 * DSC_DEVICE_ALIGN;
-        if (ctx->scratch.capacity() < (size_t) bins * csz + (size_t) M * rb + 2 * DSC_DEVICE_ALIGN + 2 * frame_b + reserve)
+        chunk = dsc_chunk_lines(capacity, fixed, 2 * frame_b, reserve, n_lines);
+        // dsc_convolve is charged the reversed taps here too, though it allocates none: the threshold it has always had
+        if (chunk == 0 || capacity < fixed + (reverse ? 0 : (size_t) M * rb) + 2 * frame_b + reserve)
             DSC_LOG_FATAL("scratch arena too small: a convolution in %d-point blocks needs %.2f MB of scratch", n,
                           (double) ((size_t) bins * csz + (size_t) M * rb + 4 * frame_b) / 1048576.);
-        chunk = (long long) ((cap / 2 < kChunkCapBytes ? cap / 2 : kChunkCapBytes) / (2 * frame_b));
-        if (chunk < 1) chunk = 1;
-        const long long room = (long long) ((cap - reserve) / (2 * frame_b));
-        if (chunk > room) chunk = room;
-        if (chunk > n_lines) chunk = n_lines;
-        frames = ctx->scratch.alloc((size_t) chunk * frame_b);
-        filtered = ctx->scratch.alloc((size_t) chunk * frame_b);
+        frames = held.alloc((size_t) chunk * frame_b);
+        filtered = held.alloc((size_t) chunk * frame_b);
     }
-    ctx->scratch.pin();
-    {
-        const dsc_tensor *hs = h;
-        dsc_tensor *hrt = nullptr;
-        if (reverse) {
-            dsc_launch_reverse(h->data, hr, M, sp, ctx->stream);
-            hrt = dsc_new_tensor_over(ctx, hr, (size_t) M * rb, 1, &M, x->dtype);
-            hs = hrt;
-        }
-        dsc_tensor *Ht = dsc_new_tensor_over(ctx, Hb, (size_t) bins * csz, 1, &bins, cdt);
-        dsc_rfft(ctx, hs, Ht, n, -1);
-        dsc_tensor_free(ctx, Ht);
-        if (hrt != nullptr) dsc_tensor_free(ctx, hrt);
+    held.pin();
+    dsc_scoped_view Ht(ctx, Hb, 1, &bins, cdt);
+    if (reverse) {
+        dsc_launch_reverse(h->data, hr, M, sp, ctx->stream);
+        dsc_scoped_view hrt(ctx, hr, 1, &M, x->dtype);
+        dsc_rfft(ctx, hrt, Ht, n, -1);
+    } else {
+        dsc_rfft(ctx, h, Ht, n, -1);
     }
 
     if (fused) {
@@ -163,25 +140,18 @@ dsc_tensor *conv_impl(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h, in
                                  (int) n_blocks, hop, pad, D, (int) T_out, sp, (int) (nr * T * (long long) rb), (int) (nr * T_out * (long long) rb),
                                  plan->tw_full, plan->tw_real, ctx->stream);
         }
-        ctx->scratch.unpin();
         ctx->last_fft_path = "conv_regs";
         return out;
     }
 
-    dsc_tensor *Ht = dsc_new_tensor_over(ctx, Hb, (size_t) bins * csz, 1, &bins, cdt);
     for (long long q = 0; q < n_lines; q += chunk) {
         const int nl = (int) (n_lines - q < chunk ? n_lines - q : chunk);
         dsc_launch_stft_frames(x->data, nullptr, frames, q, nl, n, T, (int) n_blocks, hop, pad, false, sp, ctx->stream);
         const int fshape[2] = {nl, n};
-        dsc_tensor *ft = dsc_new_tensor_over(ctx, frames, (size_t) nl * frame_b, 2, fshape, x->dtype);
-        dsc_tensor *yt = dsc_new_tensor_over(ctx, filtered, (size_t) nl * frame_b, 2, fshape, x->dtype);
+        dsc_scoped_view ft(ctx, frames, 2, fshape, x->dtype), yt(ctx, filtered, 2, fshape, x->dtype);
         dsc_filter_fft(ctx, ft, Ht, yt);
         dsc_launch_conv_crop(filtered, out->data, q, nl, n, D, (int) n_blocks, T_out, sp, ctx->stream);
-        dsc_tensor_free(ctx, ft);
-        dsc_tensor_free(ctx, yt);
     }
-    dsc_tensor_free(ctx, Ht);
-    ctx->scratch.unpin();
     ctx->last_fft_path = "conv_composed";
     return out;
 }

@@ -10,9 +10,7 @@
 //                                 dsc_irfft2 always takes this route.
 #include "dsc_internal.h"
 #include "kernels.h"
-
-#include <cstdlib>
-#include <cstring>
+#include "op_common.h"
 
 namespace {
 
@@ -42,17 +40,15 @@ dsc_tensor *fft2_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n0
     memcpy(out_shape, x->shape, sizeof(out_shape));
     out_shape[DSC_MAX_DIMS - 2] = N0;
     out_shape[DSC_MAX_DIMS - 1] = out_w;
-    if (out != nullptr) {
-        if (out->dtype != out_dtype || out->n_dim != x->n_dim || memcmp(out_shape, out->shape, sizeof(out_shape)) != 0)
-            DSC_LOG_FATAL("out must have the result's dtype and shape [.., %d, %d]", N0, out_w);
+    if (out != nullptr) {                                          // allocated late: the composed route leaves it to its second operator
+        DSC_RESULT(out, ctx, x->n_dim, out_shape, out_dtype, "the result's dtype and shape [.., %d, %d]", N0, out_w);
         if (out->data == x->data && !((kind == K_FFT2 || kind == K_IFFT2) && cplx && h == N0 && w == N1))
             DSC_LOG_FATAL("in place only for a complex fft2 / ifft2 whose image already has the transform's size");
     }
 
     const long long n_img = (long long) x->ne / ((long long) h * w);
     const dsc_fft_mode mode = kind == K_RFFT2 ? DSC_MODE_R2C_PACKED : kind == K_IRFFT2 ? DSC_MODE_C2R_PACKED : cplx ? DSC_MODE_C2C : DSC_MODE_R2C_CAST;
-    const bool fused_off = getenv("DSC_NO_FFT2_FUSED") != nullptr;        // read at every call: tools/bench_fft2.py interleaves the routes
-    bool fused = !fused_off && dsc_fft2_regs_supports(N0, N1, mode);
+    bool fused = !dsc_env_set("DSC_NO_FFT2_FUSED") && dsc_fft2_regs_supports(N0, N1, mode);
     if (fused) {
         // a workgroup addresses its images through one descriptor with 31-bit byte offsets
         const long long group_b = (long long) dsc_fft2_regs_group(N0, N1, mode, sp) * h * w * (long long) dsc_dtype_size(x->dtype);

@@ -15,13 +15,12 @@
 //                                         (fft_hilbert.hip).  f32 rows of 131072 points and more are widened to f64 for the filter.
 #include "dsc_internal.h"
 #include "kernels.h"
+#include "op_common.h"
 
-#include <cstdlib>
-#include <cstring>
+#include <climits>
 
 namespace {
 
-constexpr size_t kChunkCapBytes = (size_t) 128 << 20;     // filtered (and widened) rows per scratch chunk: at most this many bytes
 constexpr int kF32WideMinN = 131072;                      // f32 rows from this length on are filtered in f64
 
 dsc_tensor *hilbert_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n, bool envelope) {
@@ -35,7 +34,7 @@ dsc_tensor *hilbert_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int
 
     const bool sp = x->dtype == DSC_F32;
     const dsc_dtype cdt = sp ? DSC_C32 : DSC_C64, odt = envelope ? x->dtype : cdt;
-    const size_t rb = sp ? 4 : 8, csz = 2 * rb, ob = envelope ? rb : csz;
+    const size_t rb = sp ? 4 : 8;
     // f32 rows of 131072 points and more — longer than any fused f32 filter kernel — are filtered in f64: an f32 transform of that length
     // leaves more than tau 8 ||x|| / sqrt(N) on the weak samples of a row whose energy sits in a few strong ones (a single impulse:
     // 1.34 of the envelope's bound at N = 131072, on this route and on the hand composition ifft(fft(x) * h) alike).  The real part
@@ -46,22 +45,15 @@ dsc_tensor *hilbert_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int
     int out_shape[DSC_MAX_DIMS];
     memcpy(out_shape, x->shape, sizeof(out_shape));
     out_shape[DSC_MAX_DIMS - 1] = N;
-    if (out == nullptr) {
-        out = dsc_new_tensor(ctx, x->n_dim, &out_shape[DSC_MAX_DIMS - x->n_dim], odt, nullptr);
-    } else {
-        if (out->dtype != odt || out->n_dim != x->n_dim || memcmp(out_shape, out->shape, sizeof(out_shape)) != 0)
-            DSC_LOG_FATAL("out must have the %s dtype and shape [.., %d]", envelope ? "input's" : "input's complex", N);
-        const char *xa = (const char *) x->data, *oa = (const char *) out->data;
-        if (oa < xa + (size_t) x->ne * rb && xa < oa + (size_t) out->ne * ob) DSC_LOG_FATAL("out must not share memory with x");
-    }
+    DSC_RESULT(out, ctx, x->n_dim, out_shape, odt, "the %s dtype and shape [.., %d]", envelope ? "input's" : "input's complex", N);
+    DSC_NO_OVERLAP(out, x, "x");
     if (rows == 0) return out;
     const int in_len = T < N ? T : N;
 
     // fused: a workgroup holds up to 64 rows and addresses their samples with 31-bit byte offsets from its first row — 64 T elem < 2^30,
     // the condition of dsc_filter_fft.  Its rows of out are 2 N elem each and a group's transform lengths add up to at most 2^15
     // points: 1 MiB of output per group, always addressable.
-    const bool fused_off = getenv("DSC_NO_HILBERT_FUSED") != nullptr;      // read at every call: tools/bench_hilbert.py interleaves the routes
-    if (!fused_off && dsc_hilbert_regs_supports(N) && (long long) T * 8 * 64 < (1LL << 30)) {
+    if (!dsc_env_set("DSC_NO_HILBERT_FUSED") && dsc_hilbert_regs_supports(N) && (long long) T * 8 * 64 < (1LL << 30)) {
         dsc_launch_hilbert_regs(x->data, out->data, rows, N, envelope, sp, plan->tw_full, plan->tw_real, T, in_len, ctx->stream);
         ctx->last_fft_path = envelope ? "envelope_regs" : "hilbert_regs";
         return out;
@@ -75,41 +67,28 @@ dsc_tensor *hilbert_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int
     const int bins = N / 2 + 1, wpitch = in_len + (in_len & 1);
     const size_t y_b = (size_t) N * frb, w_b = wide ? (size_t) wpitch * frb : 0, frame_b = y_b + w_b, h_b = (size_t) bins * 2 * frb;
     const size_t reserve = 2 * y_b + 4 * DSC_DEVICE_ALIGN;
-    ctx->scratch.reset();
-    if (ctx->scratch.capacity() < h_b + 3 * DSC_DEVICE_ALIGN + frame_b + reserve)
+    dsc_scratch_pin held(ctx);
+    // rounded before it is bounded by the rows, hence no bound in the call
+    long long chunk = dsc_chunk_lines(ctx->scratch.capacity(), h_b + 3 * DSC_DEVICE_ALIGN, frame_b, reserve, LLONG_MAX);
+    if (chunk == 0)
         DSC_LOG_FATAL("scratch arena too small: an analytic signal of %d points needs %.2f MB of scratch", N,
                       (double) (h_b + frame_b + 2 * y_b) / 1048576.);
-    const size_t cap = ctx->scratch.capacity() - (h_b + 3 * DSC_DEVICE_ALIGN);
-    long long chunk = (long long) ((cap / 2 < kChunkCapBytes ? cap / 2 : kChunkCapBytes) / frame_b);
-    if (chunk < 1) chunk = 1;
-    const long long room = (long long) ((cap - reserve) / frame_b);
-    if (chunk > room) chunk = room;
     if (chunk > 4) chunk &= ~3LL;                                  // chunks start on whole 16-byte packs of out whatever N
     if (chunk > rows) chunk = rows;
-    char *Hb = ctx->scratch.alloc(h_b);
-    char *filtered = ctx->scratch.alloc((size_t) chunk * y_b);
-    char *widened = wide ? ctx->scratch.alloc((size_t) chunk * w_b) : nullptr;
-    ctx->scratch.pin();
+    char *Hb = held.alloc(h_b);
+    char *filtered = held.alloc((size_t) chunk * y_b);
+    char *widened = wide ? held.alloc((size_t) chunk * w_b) : nullptr;
+    held.pin();
     dsc_launch_hilbert_response(Hb, N, !wide && sp, ctx->stream);
-    dsc_tensor *Ht = dsc_new_tensor_over(ctx, Hb, h_b, 1, &bins, fcdt);
+    dsc_scoped_view Ht(ctx, Hb, 1, &bins, fcdt);
     for (long long q = 0; q < rows; q += chunk) {
         const int nl = (int) (rows - q < chunk ? rows - q : chunk);
         const int xshape[2] = {nl, wide ? wpitch : T}, yshape[2] = {nl, N};
-        dsc_tensor *xt;
-        if (wide) {
-            dsc_launch_hilbert_widen(x->data, widened, q, nl, T, in_len, wpitch, ctx->stream);
-            xt = dsc_new_tensor_over(ctx, widened, (size_t) nl * w_b, 2, xshape, fdt);
-        } else {
-            xt = dsc_new_tensor_over(ctx, (char *) x->data + (size_t) q * T * rb, (size_t) nl * T * rb, 2, xshape, fdt);
-        }
-        dsc_tensor *yt = dsc_new_tensor_over(ctx, filtered, (size_t) nl * y_b, 2, yshape, fdt);
+        if (wide) dsc_launch_hilbert_widen(x->data, widened, q, nl, T, in_len, wpitch, ctx->stream);
+        dsc_scoped_view xt(ctx, wide ? widened : (char *) x->data + (size_t) q * T * rb, 2, xshape, fdt), yt(ctx, filtered, 2, yshape, fdt);
         dsc_filter_fft(ctx, xt, Ht, yt);
         dsc_launch_hilbert_zip(x->data, filtered, out->data, q, nl, N, T, in_len, envelope, sp, wide, ctx->stream);
-        dsc_tensor_free(ctx, xt);
-        dsc_tensor_free(ctx, yt);
     }
-    dsc_tensor_free(ctx, Ht);
-    ctx->scratch.unpin();
     ctx->last_fft_path = envelope ? "envelope_composed" : "hilbert_composed";
     return out;
 }

@@ -20,9 +20,9 @@
 // buffers at one rate designs once with dsc_firwin and passes `taps`.
 #include "dsc_internal.h"
 #include "kernels.h"
+#include "op_common.h"
 
 #include <cmath>
-#include <cstring>
 #include <vector>
 
 namespace {
@@ -58,15 +58,11 @@ dsc_tensor *result_of(dsc_ctx *ctx, const dsc_tensor *x, long long T_out, dsc_te
     const int T = x->shape[DSC_MAX_DIMS - 1];
     const long long rows = x->ne / T;
     if (T_out > 0x7fffffffLL || rows * T_out > 0x7fffffffLL) DSC_LOG_FATAL("output exceeds the tensor size limit of 2^31 - 1 elements");
-    const size_t rb = dsc_dtype_size(x->dtype);
     int out_shape[DSC_MAX_DIMS];
     memcpy(out_shape, x->shape, sizeof(out_shape));
     out_shape[DSC_MAX_DIMS - 1] = (int) T_out;
-    if (out == nullptr) return dsc_new_tensor(ctx, x->n_dim, &out_shape[DSC_MAX_DIMS - x->n_dim], x->dtype, nullptr);
-    if (out->dtype != x->dtype || out->n_dim != x->n_dim || memcmp(out_shape, out->shape, sizeof(out_shape)) != 0)
-        DSC_LOG_FATAL("out must have the input's dtype and shape [.., %lld]", T_out);
-    const char *xa = (const char *) x->data, *oa = (const char *) out->data;
-    if (oa < xa + (size_t) x->ne * rb && xa < oa + (size_t) out->ne * rb) DSC_LOG_FATAL("out must not share memory with x");
+    DSC_RESULT(out, ctx, x->n_dim, out_shape, x->dtype, "the input's dtype and shape [.., %lld]", T_out);
+    DSC_NO_OVERLAP(out, x, "x");
     return out;
 }
 
@@ -74,13 +70,8 @@ dsc_tensor *result_of(dsc_ctx *ctx, const dsc_tensor *x, long long T_out, dsc_te
 dsc_tensor *polyphase(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *h, double gain, int up, int down, long long t0, long long T_out,
                       dsc_tensor *out) {
     const int T = x->shape[DSC_MAX_DIMS - 1], M = h->ne;
-    const bool own_out = out == nullptr;
     out = result_of(ctx, x, T_out, out);
-    if (!own_out) {                                                // every workgroup reads h while others already write
-        const size_t rb = dsc_dtype_size(x->dtype);
-        const char *ha = (const char *) h->data, *oa = (const char *) out->data;
-        if (oa < ha + (size_t) M * rb && ha < oa + (size_t) out->ne * rb) DSC_LOG_FATAL("out must not share memory with the filter");
-    }
+    DSC_NO_OVERLAP(out, h, "the filter");                          // every workgroup reads h while others already write
     const long long rows = x->ne / T;
     if (!dsc_launch_polyphase(x->data, h->data, out->data, rows, T, T_out, M, up, down, t0, gain, x->dtype == DSC_F32, ctx->stream))
         DSC_LOG_FATAL("up = %d, down = %d with %d taps: the taps and the samples of a 64-output tile exceed the %zu KiB of LDS", up, down, M,

@@ -17,9 +17,7 @@
 // DSC_SCAN_ROUTE=rows|tiles, read at every call, forces either route on any inner == 1 shape.
 #include "dsc_internal.h"
 #include "kernels.h"
-
-#include <cstdlib>
-#include <cstring>
+#include "op_common.h"
 
 namespace {
 
@@ -46,12 +44,8 @@ dsc_tensor *result_of(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, dsc_dt
     int out_shape[DSC_MAX_DIMS];
     memcpy(out_shape, x->shape, sizeof(out_shape));
     out_shape[v.slot] = n_out;
-    if (out == nullptr) return dsc_new_tensor(ctx, x->n_dim, &out_shape[DSC_MAX_DIMS - x->n_dim], odt, nullptr);
-    if (out->dtype != odt || out->n_dim != x->n_dim || memcmp(out_shape, out->shape, sizeof(out_shape)) != 0)
-        DSC_LOG_FATAL("out must have the result's dtype and shape (%d along the axis)", n_out);
-    const char *xa = (const char *) x->data, *oa = (const char *) out->data;
-    if (oa < xa + (size_t) x->ne * dsc_dtype_size(x->dtype) && xa < oa + (size_t) out->ne * dsc_dtype_size(odt))
-        DSC_LOG_FATAL("out must not share memory with the input");
+    DSC_RESULT(out, ctx, x->n_dim, out_shape, odt, "the result's dtype and shape (%d along the axis)", n_out);
+    DSC_NO_OVERLAP(out, x, "the input");
     return out;
 }
 

@@ -11,15 +11,12 @@
 //                  squared-window envelope over the same frames, crop of n_fft/2 (center) and trim / zero fill to `length`
 #include "dsc_internal.h"
 #include "kernels.h"
+#include "op_common.h"
 
 #include <cmath>
-#include <cstdlib>
-#include <cstring>
 #include <vector>
 
 namespace {
-
-constexpr size_t kChunkCapBytes = (size_t) 128 << 20;     // frames per scratch chunk: at most this many bytes
 
 void check_common(int n_fft, int hop, const dsc_tensor *window, dsc_dtype real_dtype) {
     if (n_fft < 4 || n_fft > (1 << 20) || (n_fft & (n_fft - 1)) != 0)
@@ -31,18 +28,14 @@ void check_common(int n_fft, int hop, const dsc_tensor *window, dsc_dtype real_d
     }
 }
 
-// frames of the scratch chunk: half the arena (at most kChunkCapBytes), leaving the inner transform routes room for two frames
+// frames of the scratch chunk (nothing else pinned), leaving the inner transform routes room for two frames
 long long chunk_frames(dsc_ctx *ctx, size_t frame_b, long long n_lines) {
-    const size_t cap = ctx->scratch.capacity();
     const size_t reserve = 2 * frame_b + 4 * DSC_DEVICE_ALIGN;
-    if (cap < frame_b + reserve)
+    const long long chunk = dsc_chunk_lines(ctx->scratch.capacity(), 0, frame_b, reserve, n_lines);
+    if (chunk == 0)
         DSC_LOG_FATAL("scratch arena too small: a short-time transform of %zu-byte frames needs %.2f MB of scratch", frame_b,
                       (double) (frame_b + reserve) / 1048576.);
-    long long chunk = (long long) ((cap / 2 < kChunkCapBytes ? cap / 2 : kChunkCapBytes) / frame_b);
-    if (chunk < 1) chunk = 1;
-    const long long room = (long long) ((cap - reserve) / frame_b);
-    if (chunk > room) chunk = room;
-    return chunk < n_lines ? chunk : n_lines;
+    return chunk;
 }
 
 // Smallest squared-window envelope env(p) = sum over frames f in [0, n_frames) with 0 <= p - f hop < n_fft of w2[p - f hop], over the
@@ -110,26 +103,14 @@ extern "C" dsc_tensor *dsc_stft(dsc_ctx *ctx, const dsc_tensor *x, int n_fft, in
     for (int i = 0; i < DSC_MAX_DIMS - 1; ++i) out_shape[i] = x->shape[i + 1];
     out_shape[DSC_MAX_DIMS - 2] = (int) n_frames;
     out_shape[DSC_MAX_DIMS - 1] = bins;
-    const int out_ndim = x->n_dim + 1;
-    if (out == nullptr) {
-        out = dsc_new_tensor(ctx, out_ndim, &out_shape[DSC_MAX_DIMS - out_ndim], cdt, nullptr);
-    } else {
-        DSC_ASSERT(out->dtype == cdt && out->n_dim == out_ndim);
-        DSC_ASSERT(memcmp(out_shape, out->shape, sizeof(out_shape)) == 0);
-    }
+    DSC_RESULT(out, ctx, x->n_dim + 1, out_shape, cdt, "the input's complex dtype and shape [.., %lld, %d]", n_frames, bins);
     const size_t rb = sp ? 4 : 8, csz = 2 * rb;
     const void *w = window != nullptr ? window->data : nullptr;
 
-    // fused: rows per launch such that every offset of the buffer descriptor over x fits 31 bits (one spare row: groups past
-    // the last line compute their offsets from row `rows`).  A row too long for even one per launch takes the composed route below
-    // (64-bit gather indices) at any n_fft.
-    const bool fused_off = getenv("DSC_NO_STFT_FUSED") != nullptr;             // read at every call: tools/bench_stft.py interleaves the routes
-    long long rows_per = ((long long) 0x7f000000 - (long long) n_fft * (long long) rb) / ((long long) T * (long long) rb) - 1;
-    // An even number of rows per launch keeps every launch's first element even (as conv.cpp does), so that pairs the kernel finds
-    // aligned relative to its base are aligned in memory too; with odd T a row too long for two per launch takes the composed route.
-    if (rows_per > 1) rows_per &= ~1LL;
-    const bool launch_aligned = rows_per != 1 || rows == 1 || (T & 1) == 0;
-    if (!fused_off && dsc_stft_regs_supports(n_fft) && rows_per >= 1 && launch_aligned) {
+    // fused: rows per launch such that every offset of the buffer descriptor over x (plus a frame past its end) fits 31 bits.  A row
+    // too long for that takes the composed route below (64-bit gather indices) at any n_fft.
+    const long long rows_per = dsc_fused_rows_per_launch(0x7f000000LL - (long long) n_fft * (long long) rb, (long long) T * (long long) rb, 0, rows, T & 1);
+    if (!dsc_env_set("DSC_NO_STFT_FUSED") && dsc_stft_regs_supports(n_fft) && rows_per > 0) {
         const dsc_fft_plan *plan = dsc_plan_fft(ctx, n_fft / 2, DSC_FFT_REAL, cdt);
         for (long long r = 0; r < rows; r += rows_per) {
             const long long nr = rows - r < rows_per ? rows - r : rows_per;
@@ -143,21 +124,17 @@ extern "C" dsc_tensor *dsc_stft(dsc_ctx *ctx, const dsc_tensor *x, int n_fft, in
 
     // composed: frames of one chunk in a pinned scratch block, the rfft routes below it
     const size_t frame_b = (size_t) n_fft * rb;
-    ctx->scratch.reset();
+    dsc_scratch_pin held(ctx);
     const long long chunk = chunk_frames(ctx, frame_b, n_lines);
-    char *frames = ctx->scratch.alloc((size_t) chunk * frame_b);
-    ctx->scratch.pin();
+    char *frames = held.alloc((size_t) chunk * frame_b);
+    held.pin();
     for (long long q = 0; q < n_lines; q += chunk) {
         const int nl = (int) (n_lines - q < chunk ? n_lines - q : chunk);
         dsc_launch_stft_frames(x->data, w, frames, q, nl, n_fft, T, (int) n_frames, hop, pad, reflect, sp, ctx->stream);
         const int fshape[2] = {nl, n_fft}, bshape[2] = {nl, bins};
-        dsc_tensor *ft = dsc_new_tensor_over(ctx, frames, (size_t) nl * frame_b, 2, fshape, x->dtype);
-        dsc_tensor *bt = dsc_new_tensor_over(ctx, (char *) out->data + (size_t) q * bins * csz, (size_t) nl * bins * csz, 2, bshape, cdt);
+        dsc_scoped_view ft(ctx, frames, 2, fshape, x->dtype), bt(ctx, (char *) out->data + (size_t) q * bins * csz, 2, bshape, cdt);
         dsc_rfft(ctx, ft, bt, n_fft, -1);
-        dsc_tensor_free(ctx, ft);
-        dsc_tensor_free(ctx, bt);
     }
-    ctx->scratch.unpin();
     ctx->last_fft_path = "stft_composed";
     return out;
 }
@@ -203,29 +180,20 @@ extern "C" dsc_tensor *dsc_istft(dsc_ctx *ctx, const dsc_tensor *X, int n_fft, i
     int out_shape[DSC_MAX_DIMS];
     for (int i = 0; i < DSC_MAX_DIMS; ++i) out_shape[i] = i == 0 ? 1 : X->shape[i - 1];
     out_shape[DSC_MAX_DIMS - 1] = (int) len;
-    const int out_ndim = X->n_dim - 1;
-    if (out == nullptr) {
-        out = dsc_new_tensor(ctx, out_ndim, &out_shape[DSC_MAX_DIMS - out_ndim], rdt, nullptr);
-    } else {
-        DSC_ASSERT(out->dtype == rdt && out->n_dim == out_ndim);
-        DSC_ASSERT(memcmp(&out_shape[DSC_MAX_DIMS - out_ndim], &out->shape[DSC_MAX_DIMS - out_ndim], out_ndim * sizeof(int)) == 0);
-    }
+    DSC_RESULT(out, ctx, X->n_dim - 1, out_shape, rdt, "the input's real dtype and shape [.., %lld]", len);
     const void *w = window != nullptr ? window->data : nullptr;
 
     const size_t frame_b = (size_t) n_fft * rb;
     const long long n_lines = rows * n_frames;
-    ctx->scratch.reset();
+    dsc_scratch_pin held(ctx);
     const long long chunk = chunk_frames(ctx, frame_b, n_lines);
-    char *frames = ctx->scratch.alloc((size_t) chunk * frame_b);
-    ctx->scratch.pin();
+    char *frames = held.alloc((size_t) chunk * frame_b);
+    held.pin();
     // frames [first, first + n) of the flattened (row, frame) list -> the pinned block
     auto irfft_frames = [&](long long first, int n) {
         const int bshape[2] = {n, bins}, fshape[2] = {n, n_fft};
-        dsc_tensor *bt = dsc_new_tensor_over(ctx, (char *) X->data + (size_t) first * bins * csz, (size_t) n * bins * csz, 2, bshape, X->dtype);
-        dsc_tensor *ft = dsc_new_tensor_over(ctx, frames, (size_t) n * frame_b, 2, fshape, rdt);
+        dsc_scoped_view bt(ctx, (char *) X->data + (size_t) first * bins * csz, 2, bshape, X->dtype), ft(ctx, frames, 2, fshape, rdt);
         dsc_irfft(ctx, bt, ft, -1, -1);
-        dsc_tensor_free(ctx, bt);
-        dsc_tensor_free(ctx, ft);
     };
     const long long p_end = (long long) pad + len;
     if (n_frames <= chunk) {                                   // whole rows per chunk
@@ -255,7 +223,6 @@ extern "C" dsc_tensor *dsc_istft(dsc_ctx *ctx, const dsc_tensor *X, int n_fft, i
             }
         }
     }
-    ctx->scratch.unpin();
     ctx->last_fft_path = "istft_ola";
     return out;
 }

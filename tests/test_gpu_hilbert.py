@@ -312,6 +312,65 @@ def test_fused_route_needs_no_scratch(kind, dt, N):
     assert f'path {kind}_regs' in r.stdout
 
 
+CHUNKS = r'''
+import sys
+import numpy as np
+import dsc_amd as dsc
+kind, scratch, src, dst = sys.argv[1], int(sys.argv[2]), sys.argv[3], sys.argv[4]
+dsc.init(64 << 20, scratch)
+y = getattr(dsc, kind)(dsc.from_numpy(np.load(src)))
+print('path', dsc.last_fft_path())
+np.save(dst, y.numpy())
+print('chunks ok')
+'''
+
+
+def composed_chunk(capacity, N, T, dt):
+    """rows per chunk of the composed route in a scratch arena of `capacity` bytes, before and after the rounding to a multiple of 4 and
+    without the bound by the rows: hilbert.cpp's call of dsc_chunk_lines (op_common.h) restated.  Pinned next to the chunk: H, N / 2 + 1
+    complex values, and 3 x 256 bytes of alignment slack; a line is a filtered row and, for f32 rows of 131072 points and more (filtered
+    in f64), the widened row next to it; the inner routes keep two filtered rows and 1024 bytes."""
+    frb = 8 if dt == F32 and N >= 131072 else dt.itemsize
+    y_b = N * frb
+    line = y_b + (min(T, N) + min(T, N) % 2) * frb * (frb != dt.itemsize)
+    cap = capacity - ((N // 2 + 1) * 2 * frb + 768)
+    reserve = 2 * y_b + 1024
+    assert cap >= line + reserve
+    chunk = max(1, min(min(cap // 2, 128 << 20) // line, (cap - reserve) // line))
+    return chunk, chunk & ~3 if chunk > 4 else chunk
+
+
+# (kind, dtype, N, rows, scratch bytes, rows per chunk before and after rounding).  N = 1024: capacity - (513 * 8 + 768) in
+# [49152, 57344) for f32 and capacity - (513 * 16 + 768) in [98304, 114688) for f64 make half of it 6 rows of 4096 / 8192 bytes, rounded
+# down to 4: chunks of 4, 4 and 3 rows.  N = 131072, f32: a line is 2 MiB (a filtered and a widened f64 row); capacity - (65537 * 16 +
+# 768) = 9 MiB and a few bytes makes half of it 2 lines: chunks of 2, 2 and 1 rows.  About 5 MiB stay unpinned, less than the 8 MiB and more that the
+# one-launch f64 transform of 131072 points asks for (dsc_fft_fused_l2_scratch_bytes), so the inner rfft / irfft take the two-pass route
+# (r2c_2pass_regs / c2r_2pass_regs) with its one row of 65536 complex values, 1 MiB, per row of the chunk.
+CHUNK_CASES = [('hilbert', F32, 1024, 11, 58112, (6, 4)), ('envelope', F32, 1024, 11, 58112, (6, 4)),
+               ('hilbert', F64, 1024, 11, 115456, (6, 4)), ('envelope', F64, 1024, 11, 115456, (6, 4)),
+               ('hilbert', F32, 131072, 5, 10486784, (2, 2))]
+
+
+@pytest.mark.parametrize('kind,dt,N,rows,scratch,chunk', CHUNK_CASES, ids=str)
+def test_composed_route_in_several_chunks(tmp_path, record_property, kind, dt, N, rows, scratch, chunk):
+    """the composed route with fewer rows per chunk than rows: the q > 0 offsets into x, the widened chunk and out, the rounding of the chunk
+    to a multiple of 4 and a shorter last chunk.  Every element of every row against the reference."""
+    assert composed_chunk(scratch, N, N, dt) == chunk and chunk[1] < rows
+    x = spiced_rows(np.random.default_rng([N, dt.itemsize, 11]), rows, N, dt)
+    src, dst = str(tmp_path / 'x.npy'), str(tmp_path / 'y.npy')
+    np.save(src, x)
+    r = subprocess.run([sys.executable, '-c', CHUNKS, kind, str(scratch), src, dst], cwd=ROOT, capture_output=True, text=True, timeout=300,
+                       env=dict(os.environ, **{SWITCH: '1'}))
+    assert r.returncode == 0 and 'chunks ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])
+    assert f'path {kind}_composed' in r.stdout
+    yh = np.load(dst)
+    assert yh.shape == (rows, N) and yh.dtype == (CPX[dt] if kind == 'hilbert' else dt)
+    ratio = err_ratio(kind, yh, x, None)
+    record_property(f'{kind}_composed:{dt} (chunked)', ratio)
+    print(f'{kind}_composed {dt} [{rows}, {N}] in chunks of {chunk[1]}: err / bound = {ratio:.3g}')
+    assert ratio <= 1, ratio
+
+
 ERRORS = {
     'hilbert_of_complex': ("dsc.hilbert(dsc.from_numpy(np.ones((2, 512), np.complex64)))", 'input must be real'),
     'envelope_of_complex': ("dsc.envelope(dsc.from_numpy(np.ones((2, 64), np.complex128)))", 'input must be real'),

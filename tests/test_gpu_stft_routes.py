@@ -327,9 +327,10 @@ def test_inverse_every_length(dsc, record_property, n_fft, dt, i):
 
 # ---------------------------------------------------------------------------------------------------- (f) inverse, chunking
 
-# chunk_frames (stft.cpp) for a scratch arena of `cap` bytes and frames of frame_b = n_fft * sizeof(real) bytes:
+# dsc_chunk_lines (op_common.h), as stft.cpp calls it for a scratch arena of `cap` bytes with nothing else pinned and lines of
+# frame_b = n_fft * sizeof(real) bytes, the reserve 2 frame_b + 1024:
 #     chunk = min(min(cap / 2, 128 MB) / frame_b, (cap - 2 frame_b - 1024) / frame_b, rows * n_frames)
-# and it exits when cap < 3 frame_b + 1024.  A scratch arena of 2 c frame_b bytes (c >= 2) therefore gives chunk = c frames, and
+# and stft.cpp exits when cap < 3 frame_b + 1024.  A scratch arena of 2 c frame_b bytes (c >= 2) therefore gives chunk = c frames, and
 # dsc_init takes the scratch size as passed (rounded up to 256 B).  With n_frames > chunk the frame-window branch runs and needs
 # chunk > ceil(n_fft / hop); with n_frames <= chunk < rows * n_frames whole rows go chunk / n_frames at a time.
 CHUNKED = r'''

@@ -7,11 +7,15 @@
 --run     every complex length 1 .. 2^21 x rfft / irfft / fft / ifft (real and complex input) x f32 / f64 x full / zero-padded lines, on the
           last axis (2 rows from 65536 points up) and, up to 2^16, on axis 0 with 70 columns; long axis-0 lines in 16 real / 8 complex
           columns (the four-step passes at every length of the column table); every fft2 / rfft2 window; decimate / resample_poly shapes
-          for each polyphase tile form.  DSC_NO_FUSED_L2=1: rows of 65536 and 131072 points reach the two-pass launcher.  Prints one
-          line per call, 'CALL ... <dsc.last_fft_path()>'.
+          for each polyphase tile form.  DSC_NO_FUSED_L2=1: rows of 65536 and 131072 points reach the two-pass launcher.  Then the
+          operators (stft, istft, convolve, correlate, hilbert, envelope, fft2, cumsum, unwrap, diff, resample_poly): one small call per
+          route, the composed routes with their DSC_NO_..._FUSED switch set around the call, scan_rows / scan_tiles through
+          DSC_SCAN_ROUTE, and the chunked branches of stft, istft, convolve, correlate, hilbert and envelope at n = 1024 in a second
+          context with 64 KiB of scratch, three chunks each.  Prints one line per call, 'CALL ... <dsc.last_fft_path()>'.
 --compare the kernel-trace CSVs below the two directories in dispatch order: the same sequence of (Kernel_Name, Grid_Size, Workgroup_Size,
           LDS_Block_Size), and the same paths.txt.  Exits 1 on a difference.
 """
+import contextlib
 import csv
 import glob
 import os
@@ -65,7 +69,74 @@ def run():
             call('decimate', lambda x: dsc.decimate(x, 2), (2, T), rdt)
         for T in (100, 260, 4096):
             call('resample_poly', lambda x: dsc.resample_poly(x, 3, 2), (2, T), rdt)
+    operators(dsc, np, call)
     dsc.synchronize()
+
+
+@contextlib.contextmanager
+def switch(name, value='1'):
+    os.environ[name] = value
+    try:
+        yield
+    finally:
+        del os.environ[name]
+
+
+def operators(dsc, np, call):
+    F32, F64 = np.float32, np.float64
+    cpx = {F32: np.complex64, F64: np.complex128}
+
+    def ones(n, dt):
+        return dsc.from_numpy(np.ones(n, dtype=dt))
+
+    def signal_ops(dt, stft_T, spectrum, conv_T, hilbert_rows):
+        """stft / istft / convolve / correlate / hilbert / envelope at n = 1024 on whichever route the switches and the context give"""
+        call('stft', lambda x: dsc.stft(x, 1024, 256), (1, stft_T), dt)
+        for shape in spectrum:
+            call('istft', lambda x: dsc.istft(x, 1024, 256), shape, cpx[dt])
+        for name in ('convolve', 'correlate'):
+            call(name, lambda x: getattr(dsc, name)(x, ones(63, dt), 'full'), (1, conv_T), dt)
+        for name in ('hilbert', 'envelope'):
+            call(name, getattr(dsc, name), (hilbert_rows, 1024), dt)
+
+    for dt in (F32, F64):
+        signal_ops(dt, 4864, [(2, 20, 513)], 7000, 11)                                # the fused routes (istft has one route)
+        with switch('DSC_NO_STFT_FUSED'), switch('DSC_NO_CONV_FUSED'), switch('DSC_NO_HILBERT_FUSED'):
+            signal_ops(dt, 4864, [], 7000, 11)                                         # the composed ones, one chunk
+        call('stft', lambda x: dsc.stft(x, 32, 8), (2, 300), dt)                      # lengths without a fused kernel
+        call('stft', lambda x: dsc.stft(x, 65536, 16384), (1, 1 << 17), dt)
+        call('convolve', lambda x: dsc.convolve(x, ones(40000, dt), 'same'), (1, 50000), dt)
+        call('hilbert', dsc.hilbert, (3, 64), dt)
+        call('envelope', dsc.envelope, (2, 1 << 17), dt)                              # f32: widened rows
+        for fused in (True, False):
+            with contextlib.nullcontext() if fused else switch('DSC_NO_FFT2_FUSED'):
+                call('fft2', dsc.fft2, (2, 32, 32), cpx[dt])
+                call('ifft2', dsc.ifft2, (2, 32, 32), cpx[dt])
+                call('rfft2', dsc.rfft2, (2, 32, 64), dt)
+        call('fft2', dsc.fft2, (2, 16, 512), cpx[dt])                                 # no one-pass kernel
+        call('irfft2', dsc.irfft2, (2, 32, 33), cpx[dt])
+        for route in ('rows', 'tiles'):
+            with switch('DSC_SCAN_ROUTE', route):
+                call('cumsum', dsc.cumsum, (3, 20000), dt)
+                call('unwrap', dsc.unwrap, (3, 20000), dt)
+        call('cumsum', dsc.cumsum, (3, 20000), dt)                                    # the routes chosen by shape: tiles, rows, cols
+        call('cumsum', dsc.cumsum, (200, 300), cpx[dt])
+        call('unwrap', lambda x: dsc.unwrap(x, axis=0), (300, 70), dt)
+        call('diff', dsc.diff, (3, 5000), dt)
+        call('diff', lambda x: dsc.diff(x, axis=0), (300, 70), dt)
+        call('resample_poly', lambda x: dsc.resample_poly(x, 3, 2), (2, 1000), dt)
+        call('resample_poly', lambda x: dsc.resample_poly(x, 2, 2), (2, 1000), dt)    # a copy
+        call('resample_poly', lambda x: dsc.resample_poly(x, 1, 3, taps=ones(31, dt)), (2, 1000), dt)
+
+    # Chunked.  64 KiB of scratch and lines of n = 1024: stft / istft keep 8 frames per chunk (20 frames; 5 rows of 4 frames, two rows
+    # at a time; one row of 20 frames in windows of frames), convolve / correlate in 1024-point blocks 3 blocks (8 blocks), hilbert /
+    # envelope 7 rows rounded to 4 (11 rows).  f64 in a context of twice the size.
+    for dt in (F32, F64):
+        dsc.synchronize()
+        dsc.shutdown()
+        dsc.init(256 << 20, (64 << 10) * np.dtype(dt).itemsize // 4)
+        with switch('DSC_NO_STFT_FUSED'), switch('DSC_NO_CONV_FUSED'), switch('DSC_NO_HILBERT_FUSED'), switch('DSC_CONV_N', '1024'):
+            signal_ops(dt, 4864, [(5, 4, 513), (1, 20, 513)], 7000, 11)
 
 
 def trace(d):
