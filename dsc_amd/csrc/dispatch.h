@@ -1,6 +1,7 @@
 // dispatch.h — the host-side idiom every kernel file uses to get from run-time arguments to one instantiation and to launch it.
 //   with_real / with_bool / with_mode   hand a run-time choice to a generic callable as a compile-time constant; each kernel file adds
 //                                        its own with_..._len table next to its supports() gate, and ends it with no_kernel
+//   with_index<N>                        the same for a code 0 .. N - 1 (operator codes); with_dtype is in stream_common.h
 //   dsc_launch_dyn_lds / dsc_launch_var_lds   the one place that opts a kernel in to its dynamic LDS (once per device) and launches it
 //   dsc_cu_count                         grid size of the persistent kernels
 #pragma once
@@ -8,6 +9,7 @@
 #include "kernels.h"
 
 #include <type_traits>
+#include <utility>
 
 template<int V> using int_c = std::integral_constant<int, V>;
 template<bool V> using bool_c = std::integral_constant<bool, V>;
@@ -21,6 +23,14 @@ template<bool V> using bool_c = std::integral_constant<bool, V>;
 
 template<typename F> void with_real(bool single_precision, F f) { if (single_precision) f(float{}); else f(double{}); }
 template<typename F> void with_bool(bool b, F f) { if (b) f(bool_c<true>{}); else f(bool_c<false>{}); }
+
+// value in 0 .. N - 1 -> int_c<value>; `file` and `what` name the table for no_kernel
+template<typename F, int... K> bool with_index_in(int value, F &f, std::integer_sequence<int, K...>) {
+    return ((value == K && (f(int_c<K>{}), true)) || ...);
+}
+template<int N, typename F> void with_index(const char *file, const char *what, int value, F f) {
+    if (!with_index_in(value, f, std::make_integer_sequence<int, N>{})) no_kernel(file, what, value);
+}
 
 // (mode, inverse) -> (MODE, INV): the packed-real modes have one direction each
 template<typename F> void with_mode(dsc_fft_mode mode, bool inverse, F f) {

@@ -1,4 +1,6 @@
-// elementwise.hip — dtype cast and broadcast binary operators (HBM-bound streaming kernels).
+// elementwise.hip — the HBM-bound streaming kernels that compute per element: dtype cast, the broadcast binary operators (add, sub,
+// mul, div, pow; operands of one dtype or of two, promoted in registers), the unary functions (abs .. clip) and arange.
+// The kernels that only move elements (slices, transposes) are in layout.hip.
 //
 // Reference: dsc_cast (dsc/src/dsc.cpp:536-597, cast_op dsc/include/dsc_ops.h:12-44) and
 // binary_op (dsc/src/dsc.cpp:1186-1245) with mul_op & co. (dsc_ops.h:46-90).  The reference
@@ -6,27 +8,9 @@
 // index is decomposed once per element and each operand offset is a dot product with its
 // broadcast strides (0 on broadcast dims), so equal-shape, row-broadcast and scalar operands
 // all stream at the same rate.
-#include "kernels.h"
-
-#include <hip/hip_runtime.h>
-#include <type_traits>
+#include "stream_common.h"
 
 namespace {
-
-template<typename T> struct alignas(2 * sizeof(T)) cx { T x, y; };
-
-template<typename T> struct elem;   // dtype code -> storage type
-template<> struct elem<float>  { static constexpr bool cplx = false; using real = float; };
-template<> struct elem<double> { static constexpr bool cplx = false; using real = double; };
-template<> struct elem<cx<float>>  { static constexpr bool cplx = true; using real = float; };
-template<> struct elem<cx<double>> { static constexpr bool cplx = true; using real = double; };
-
-inline dim3 stream_grid(long long ne) {
-    long long blocks = (ne + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;        // 8 blocks per CU, grid-stride beyond that
-    if (blocks < 1) blocks = 1;
-    return dim3((unsigned) blocks);
-}
 
 // Grid of the PACKED kernels (16 bytes per thread in their widest stream): one pack per thread, no loop in practice —
 // workgroups are dispatched in address order and end right after their store, so the whole chip sweeps one window of memory:
@@ -43,9 +27,7 @@ inline dim3 pack_grid(long long npack) {
     return dim3((unsigned) blocks);
 }
 
-template<typename T, int V> struct alignas(sizeof(T) * V) packed { T e[V]; };
 template<typename A, typename B> constexpr int pack_width() { return 16 / (int) (sizeof(A) > sizeof(B) ? sizeof(A) : sizeof(B)); }
-inline bool aligned_to(const void *p, size_t a) { return ((size_t) p & (a - 1)) == 0; }
 
 // cast_op (dsc_ops.h:12-44): complex -> real keeps .real; real -> complex sets imag = 0
 template<typename Tin, typename Tout>
@@ -90,17 +72,6 @@ void cast_to(const Tin *x, Tout *out, long long ne, hipStream_t s) {
         done = npack * V;
     }
     if (done < ne) DSC_LAUNCH((cast_kernel<Tin, Tout>), stream_grid(ne - done), dim3(256), 0, s, x + done, out + done, ne - done);
-}
-
-template<typename Tin>
-void cast_from(const void *in, void *out, int out_dtype, long long ne, dim3, hipStream_t s) {
-    const Tin *x = (const Tin *) in;
-    switch (out_dtype) {
-        case 0: cast_to<Tin, float>(x, (float *) out, ne, s); break;
-        case 1: cast_to<Tin, double>(x, (double *) out, ne, s); break;
-        case 2: cast_to<Tin, cx<float>>(x, (cx<float> *) out, ne, s); break;
-        default: cast_to<Tin, cx<double>>(x, (cx<double> *) out, ne, s); break;
-    }
 }
 
 // ---- transcendental functions of dsc_ops.h:92-229, generic over the four element types.  Real parts go to ocml's ACCURATE
@@ -294,15 +265,16 @@ __global__ void binary_column_pack_kernel(const T *big, const T *small, T *out, 
 }
 
 template<typename T, int OP>
-bool binary_fast(const T *pa, const T *pb, T *po, const dsc_bcast_args &g, dim3 grid, hipStream_t s) {
+bool binary_fast(const T *pa, const T *pb, T *po, const dsc_bcast_args &g, hipStream_t s) {
     constexpr unsigned V = 16 / sizeof(T);
     if (g.fast >= 4 && !g.a_scalar && !g.b_scalar) {
         const bool big_is_a = g.fast == 4;
         const T *big = big_is_a ? pa : pb, *small = big_is_a ? pb : pa;
         if (g.ne % V != 0 || !aligned_to(big, 16) || !aligned_to(po, 16) || g.small_ne < (int) V) return false;
         const unsigned npack = (unsigned) (g.ne / V);
-        if (big_is_a) DSC_LAUNCH((binary_column_pack_kernel<T, OP, true>), pack_grid(npack), dim3(256), 0, s, big, small, po, npack, (unsigned) g.small_ne);
-        else          DSC_LAUNCH((binary_column_pack_kernel<T, OP, false>), pack_grid(npack), dim3(256), 0, s, big, small, po, npack, (unsigned) g.small_ne);
+        with_bool(big_is_a, [&](auto big_a) {
+            DSC_LAUNCH((binary_column_pack_kernel<T, OP, decltype(big_a)::value>), pack_grid(npack), dim3(256), 0, s, big, small, po, npack, (unsigned) g.small_ne);
+        });
         return true;
     }
     if ((g.a_scalar || g.b_scalar || g.fast == 2 || g.fast == 3) && g.ne % V == 0) {
@@ -311,8 +283,9 @@ bool binary_fast(const T *pa, const T *pb, T *po, const dsc_bcast_args &g, dim3 
         const unsigned sm = (g.a_scalar || g.b_scalar) ? 1u : (unsigned) g.small_ne;
         if (aligned_to(big, 16) && aligned_to(po, 16) && sm >= 1) {
             const unsigned npack = (unsigned) (g.ne / V);
-            if (big_is_a) DSC_LAUNCH((binary_small_pack_kernel<T, OP, true>), pack_grid(npack), dim3(256), 0, s, big, small, po, npack, sm);
-            else          DSC_LAUNCH((binary_small_pack_kernel<T, OP, false>), pack_grid(npack), dim3(256), 0, s, big, small, po, npack, sm);
+            with_bool(big_is_a, [&](auto big_a) {
+                DSC_LAUNCH((binary_small_pack_kernel<T, OP, decltype(big_a)::value>), pack_grid(npack), dim3(256), 0, s, big, small, po, npack, sm);
+            });
             return true;
         }
     }
@@ -322,9 +295,9 @@ bool binary_fast(const T *pa, const T *pb, T *po, const dsc_bcast_args &g, dim3 
         DSC_LAUNCH((binary_same_vec_kernel<T, OP>), pack_grid(ne / V), dim3(256), 0, s, pa, pb, po, ne / V);
         return true;
     }
-    if (g.fast == 1) DSC_LAUNCH((binary_fast_kernel<T, OP, 1>), grid, dim3(256), 0, s, pa, pb, po, ne, sm);
-    else if (g.fast == 2) DSC_LAUNCH((binary_fast_kernel<T, OP, 2>), grid, dim3(256), 0, s, pa, pb, po, ne, sm);
-    else DSC_LAUNCH((binary_fast_kernel<T, OP, 3>), grid, dim3(256), 0, s, pa, pb, po, ne, sm);
+    with_index<3>("elementwise.hip", "fast index path", g.fast - 1, [&](auto f) {          // g.fast is 1, 2 or 3 here
+        DSC_LAUNCH((binary_fast_kernel<T, OP, decltype(f)::value + 1>), stream_grid(g.ne), dim3(256), 0, s, pa, pb, po, ne, sm);
+    });
     return true;
 }
 
@@ -361,8 +334,8 @@ __global__ void binary_bcast_pack_kernel(const T *a, const T *b, T *out, const d
     }
 }
 
-template<typename T>
-bool binary_bcast_pack(const T *pa, const T *pb, T *po, int op, const dsc_bcast_args &g, hipStream_t s) {
+template<typename T, int OP>
+bool binary_bcast_pack(const T *pa, const T *pb, T *po, const dsc_bcast_args &g, hipStream_t s) {
     constexpr int V = 16 / sizeof(T);
     if (g.a_scalar || g.b_scalar || g.out_shape[3] % V != 0 || !aligned_to(po, 16) || g.ne / V >= (1LL << 32)) return false;
     auto fits = [&](const T *p, const int *st) {
@@ -373,46 +346,21 @@ bool binary_bcast_pack(const T *pa, const T *pb, T *po, int op, const dsc_bcast_
     };
     if (!fits(pa, g.a_stride) || !fits(pb, g.b_stride)) return false;
     const unsigned ppr = (unsigned) (g.out_shape[3] / V), npack = (unsigned) (g.ne / V);
-    switch (op) {
-        case 0: DSC_LAUNCH((binary_bcast_pack_kernel<T, 0>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
-        case 1: DSC_LAUNCH((binary_bcast_pack_kernel<T, 1>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
-        case 2: DSC_LAUNCH((binary_bcast_pack_kernel<T, 2>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
-        case 3: DSC_LAUNCH((binary_bcast_pack_kernel<T, 3>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
-        default: DSC_LAUNCH((binary_bcast_pack_kernel<T, 4>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack); break;
-    }
+    DSC_LAUNCH((binary_bcast_pack_kernel<T, OP>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, g, ppr, npack);
     return true;
 }
 
-template<typename T>
-void binary_typed(const void *a, const void *b, void *out, int op, const dsc_bcast_args &g, dim3 grid, hipStream_t s) {
-    const T *pa = (const T *) a, *pb = (const T *) b;
-    T *po = (T *) out;
-    if (op == 0 && binary_fast<T, 0>(pa, pb, po, g, grid, s)) return;
-    if (op == 1 && binary_fast<T, 1>(pa, pb, po, g, grid, s)) return;
-    if (op == 2 && binary_fast<T, 2>(pa, pb, po, g, grid, s)) return;
-    if (op == 3 && binary_fast<T, 3>(pa, pb, po, g, grid, s)) return;
-    if (op == 4 && binary_fast<T, 4>(pa, pb, po, g, grid, s)) return;
-    if (binary_bcast_pack<T>(pa, pb, po, op, g, s)) return;
+template<typename T, int OP>
+void binary_op(const T *pa, const T *pb, T *po, const dsc_bcast_args &g, hipStream_t s) {
+    if (binary_fast<T, OP>(pa, pb, po, g, s)) return;
+    if (binary_bcast_pack<T, OP>(pa, pb, po, g, s)) return;
     const long long rows = g.out_shape[3] > 0 ? g.ne / g.out_shape[3] : 0;
     const unsigned chunks = (unsigned) ((g.out_shape[3] + 1023) / 1024);
     if (!g.a_scalar && !g.b_scalar && g.out_shape[3] >= 64 && rows * chunks < (1LL << 31)) {
-        const dim3 rg((unsigned) (rows * chunks));
-        switch (op) {
-            case 0: DSC_LAUNCH((binary_rows_kernel<T, 0>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
-            case 1: DSC_LAUNCH((binary_rows_kernel<T, 1>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
-            case 2: DSC_LAUNCH((binary_rows_kernel<T, 2>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
-            case 3: DSC_LAUNCH((binary_rows_kernel<T, 3>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
-            default: DSC_LAUNCH((binary_rows_kernel<T, 4>), rg, dim3(256), 0, s, pa, pb, po, g, chunks); break;
-        }
+        DSC_LAUNCH((binary_rows_kernel<T, OP>), dim3((unsigned) (rows * chunks)), dim3(256), 0, s, pa, pb, po, g, chunks);
         return;
     }
-    switch (op) {
-        case 0: DSC_LAUNCH((binary_kernel<T, 0>), grid, dim3(256), 0, s, pa, pb, po, g); break;
-        case 1: DSC_LAUNCH((binary_kernel<T, 1>), grid, dim3(256), 0, s, pa, pb, po, g); break;
-        case 2: DSC_LAUNCH((binary_kernel<T, 2>), grid, dim3(256), 0, s, pa, pb, po, g); break;
-        case 3: DSC_LAUNCH((binary_kernel<T, 3>), grid, dim3(256), 0, s, pa, pb, po, g); break;
-        default: DSC_LAUNCH((binary_kernel<T, 4>), grid, dim3(256), 0, s, pa, pb, po, g); break;
-    }
+    DSC_LAUNCH((binary_kernel<T, OP>), stream_grid(g.ne), dim3(256), 0, s, pa, pb, po, g);
 }
 
 // abs / angle / conj / real / imag: dsc/src/dsc.cpp:1480-1622, functors dsc_ops.h:242-303.
@@ -541,34 +489,6 @@ void unary_op(const Tin *x, void *out, long long ne, const unary_params p, hipSt
     }
 }
 
-template<typename Tin>
-void unary_typed(const void *in, void *out, int op, long long ne, const unary_params p, hipStream_t s) {
-    const Tin *x = (const Tin *) in;
-    switch (op) {
-        case 0: unary_op<Tin, 0>(x, out, ne, p, s); break;
-        case 1: unary_op<Tin, 1>(x, out, ne, p, s); break;
-        case 2: unary_op<Tin, 2>(x, out, ne, p, s); break;
-        case 3: unary_op<Tin, 3>(x, out, ne, p, s); break;
-        case 4: unary_op<Tin, 4>(x, out, ne, p, s); break;
-        case 5: unary_op<Tin, 5>(x, out, ne, p, s); break;
-        case 6: unary_op<Tin, 6>(x, out, ne, p, s); break;
-        case 7: unary_op<Tin, 7>(x, out, ne, p, s); break;
-        case 8: unary_op<Tin, 8>(x, out, ne, p, s); break;
-        case 9: unary_op<Tin, 9>(x, out, ne, p, s); break;
-        case 10: unary_op<Tin, 10>(x, out, ne, p, s); break;
-        case 11: unary_op<Tin, 11>(x, out, ne, p, s); break;
-        case 12: unary_op<Tin, 12>(x, out, ne, p, s); break;
-        case 13:
-            if constexpr (!elem<Tin>::cplx) { unary_op<Tin, 13>(x, out, ne, p, s); break; }
-            fprintf(stderr, "dsc_launch_unary: i0 of a complex tensor\n");
-            exit(EXIT_FAILURE);
-        case 14: unary_op<Tin, 14>(x, out, ne, p, s); break;
-        default:
-            fprintf(stderr, "dsc_launch_unary: unknown op %d\n", op);
-            exit(EXIT_FAILURE);
-    }
-}
-
 // arange (dsc.cpp:430-439, 477-499): the reference accumulates val += 1 in T, so an f32 (or c32 real part) saturates at
 // 2^24 — 2^24 + 1 rounds back to 2^24 — and element i is min(i, 2^24); f64 is exact for every int n.
 template<typename T>
@@ -609,36 +529,39 @@ void arange_typed(void *out, long long n, hipStream_t s) {
 
 }  // namespace
 
+// in_dtype != out_dtype: both callers return the tensor itself for an equal pair, so no copy kernel is compiled for one
 void dsc_launch_cast(const void *in, int in_dtype, void *out, int out_dtype, long long ne, hipStream_t stream) {
     if (ne <= 0) return;
-    const dim3 grid = stream_grid(ne);
-    switch (in_dtype) {
-        case 0: cast_from<float>(in, out, out_dtype, ne, grid, stream); break;
-        case 1: cast_from<double>(in, out, out_dtype, ne, grid, stream); break;
-        case 2: cast_from<cx<float>>(in, out, out_dtype, ne, grid, stream); break;
-        default: cast_from<cx<double>>(in, out, out_dtype, ne, grid, stream); break;
-    }
+    with_dtype(in_dtype, [&](auto ti) {
+        with_dtype(out_dtype, [&](auto to) {
+            using Tin = decltype(ti);
+            using Tout = decltype(to);
+            if constexpr (std::is_same<Tin, Tout>::value) no_kernel("elementwise.hip", "cast to the input's own dtype", out_dtype);
+            else cast_to<Tin, Tout>((const Tin *) in, (Tout *) out, ne, stream);
+        });
+    });
 }
 
 void dsc_launch_unary(const void *in, int in_dtype, void *out, int op, long long ne, hipStream_t stream, double lo, double hi) {
     if (ne <= 0) return;
     const unary_params p{lo, hi};
-    switch (in_dtype) {
-        case 0: unary_typed<float>(in, out, op, ne, p, stream); break;
-        case 1: unary_typed<double>(in, out, op, ne, p, stream); break;
-        case 2: unary_typed<cx<float>>(in, out, op, ne, p, stream); break;
-        default: unary_typed<cx<double>>(in, out, op, ne, p, stream); break;
-    }
+    with_dtype(in_dtype, [&](auto t) {
+        with_index<15>("elementwise.hip", "unary op", op, [&](auto opc) {
+            using Tin = decltype(t);
+            constexpr int OP = decltype(opc)::value;
+            if constexpr (OP == 13 && elem<Tin>::cplx) {
+                fprintf(stderr, "dsc_launch_unary: i0 of a complex tensor\n");
+                exit(EXIT_FAILURE);
+            } else {
+                unary_op<Tin, OP>((const Tin *) in, out, ne, p, stream);
+            }
+        });
+    });
 }
 
 void dsc_launch_arange(void *out, int dtype, long long n, hipStream_t stream) {
     if (n <= 0) return;
-    switch (dtype) {
-        case 0: arange_typed<float>(out, n, stream); break;
-        case 1: arange_typed<double>(out, n, stream); break;
-        case 2: arange_typed<cx<float>>(out, n, stream); break;
-        default: arange_typed<cx<double>>(out, n, stream); break;
-    }
+    with_dtype(dtype, [&](auto t) { arange_typed<decltype(t)>(out, n, stream); });
 }
 
 // ---- operands of DIFFERENT dtypes and equal shapes: the casts of binary_op (dsc.cpp:1186-1223 casts both operands to the
@@ -676,313 +599,33 @@ bool mixed_pair(const void *a, const void *b, void *out, int op, long long ne, h
     if (ne % V != 0 || !aligned_to(a, sizeof(Ta) * V) || !aligned_to(b, sizeof(Tb) * V) || !aligned_to(out, 16)) return false;
     const unsigned npack = (unsigned) (ne / V);
     const Ta *pa = (const Ta *) a; const Tb *pb = (const Tb *) b; To *po = (To *) out;
-    switch (op) {
-        case 0: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 0>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
-        case 1: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 1>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
-        case 2: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 2>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
-        case 3: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 3>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
-        default: DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, 4>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack); break;
-    }
+    with_index<5>("elementwise.hip", "binary op", op, [&](auto opc) {
+        DSC_LAUNCH((binary_mixed_pack_kernel<Ta, Tb, decltype(opc)::value>), pack_grid(npack), dim3(256), 0, s, pa, pb, po, npack);
+    });
     return true;
-}
-
-template<typename Ta>
-bool mixed_a(const void *a, const void *b, int b_dtype, void *out, int op, long long ne, hipStream_t s) {
-    switch (b_dtype) {
-        case 0: return mixed_pair<Ta, float>(a, b, out, op, ne, s);
-        case 1: return mixed_pair<Ta, double>(a, b, out, op, ne, s);
-        case 2: return mixed_pair<Ta, cx<float>>(a, b, out, op, ne, s);
-        default: return mixed_pair<Ta, cx<double>>(a, b, out, op, ne, s);
-    }
 }
 }  // namespace
 
 bool dsc_launch_binary_mixed(const void *a, int a_dtype, const void *b, int b_dtype, void *out, int op, long long ne, hipStream_t stream) {
     if (ne <= 0 || a_dtype == b_dtype) return false;
-    switch (a_dtype) {
-        case 0: return mixed_a<float>(a, b, b_dtype, out, op, ne, stream);
-        case 1: return mixed_a<double>(a, b, b_dtype, out, op, ne, stream);
-        case 2: return mixed_a<cx<float>>(a, b, b_dtype, out, op, ne, stream);
-        default: return mixed_a<cx<double>>(a, b, b_dtype, out, op, ne, stream);
-    }
+    bool done = false;
+    with_dtype(a_dtype, [&](auto ta) {
+        with_dtype(b_dtype, [&](auto tb) {
+            using Ta = decltype(ta);
+            using Tb = decltype(tb);
+            if constexpr (std::is_same<Ta, Tb>::value) no_kernel("elementwise.hip", "mixed operands of one dtype", a_dtype);   // returned above
+            else done = mixed_pair<Ta, Tb>(a, b, out, op, ne, stream);
+        });
+    });
+    return done;
 }
 
 void dsc_launch_binary(const void *a, const void *b, void *out, int dtype, int op, const dsc_bcast_args &g, hipStream_t stream) {
     if (g.ne <= 0) return;
-    const dim3 grid = stream_grid(g.ne);
-    switch (dtype) {
-        case 0: binary_typed<float>(a, b, out, op, g, grid, stream); break;
-        case 1: binary_typed<double>(a, b, out, op, g, grid, stream); break;
-        case 2: binary_typed<cx<float>>(a, b, out, op, g, grid, stream); break;
-        default: binary_typed<cx<double>>(a, b, out, op, g, grid, stream); break;
-    }
-}
-
-// ---- slice regions: dsc_tensor_get_slice / set_slice (dsc.cpp:868-1169) ---------------------
-// The reference walks a dsc_slice_iterator (dsc_iter.h:125-190) per element; here a block owns a piece of
-// one innermost row of the region (one division chain per block), or — for narrow rows — a flat
-// per-element decomposition.
-namespace {
-
-struct alignas(16) b16 { unsigned long long a, b; };
-// elements per thread of region_rows_kernel: ONE 16-byte pack (the launch then sweeps memory in address order and every
-// workgroup ends right after its store: x[:, :60000] 67 -> 73.5 % of the roofline), four of the narrower elements (with one
-// per thread the strided x[:, ::2] drops from 49 to 35 %)
-template<typename E> constexpr int region_u() { return sizeof(E) == 16 ? 1 : 4; }
-
-template<typename E, bool SCATTER>
-__global__ void region_rows_kernel(const E *src, E *dst, const dsc_region r, unsigned chunks_per_row, long long dense_ne) {
-    const unsigned long long blk = blockIdx.x;
-    const unsigned long long row = blk / chunks_per_row;
-    const unsigned chunk = (unsigned) (blk - row * chunks_per_row);
-    const unsigned long long i01 = row / r.count[2];
-    const long long i2 = (long long) (row - i01 * r.count[2]);
-    const long long i0 = (long long) (i01 / r.count[1]), i1 = (long long) (i01 - (unsigned long long) i0 * r.count[1]);
-    const long long base = r.base + i0 * r.stride[0] + i1 * r.stride[1] + i2 * r.stride[2];
-    const long long dense0 = (long long) row * r.count[3];
-    constexpr int U = region_u<E>();
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const int c = chunk * (256 * U) + u * 256 + threadIdx.x;
-        if (c >= r.count[3]) return;
-        if (SCATTER) dst[base + c * r.stride[3]] = src[(dense0 + c) % dense_ne];
-        else         dst[dense0 + c] = src[base + c * r.stride[3]];
-    }
-}
-
-template<typename E, bool SCATTER>
-__global__ void region_flat_kernel(const E *src, E *dst, const dsc_region r, long long dense_ne) {
-    const long long s3 = r.count[3], s23 = s3 * r.count[2], s123 = s23 * r.count[1];
-    for (long long i = (long long) blockIdx.x * blockDim.x + threadIdx.x; i < r.ne; i += (long long) gridDim.x * blockDim.x) {
-        const long long i0 = i / s123, r0 = i - i0 * s123;
-        const long long i1 = r0 / s23, r1 = r0 - i1 * s23;
-        const long long i2 = r1 / s3, i3 = r1 - i2 * s3;
-        const long long at = r.base + i0 * r.stride[0] + i1 * r.stride[1] + i2 * r.stride[2] + i3 * r.stride[3];
-        if (SCATTER) dst[at] = src[i % dense_ne];
-        else         dst[i] = src[at];
-    }
-}
-
-template<typename E>
-void region_typed(const void *src, void *dst, const dsc_region &r, bool scatter, long long dense_ne, hipStream_t s) {
-    const E *ps = (const E *) src;
-    E *pd = (E *) dst;
-    const long long rows = r.ne / r.count[3];
-    constexpr int per_block = 256 * region_u<E>();
-    if (r.count[3] >= 128 && rows * ((r.count[3] + per_block - 1) / per_block) < (1LL << 31)) {
-        const unsigned chunks = (unsigned) ((r.count[3] + per_block - 1) / per_block);
-        const dim3 grid((unsigned) (rows * chunks));
-        if (scatter) DSC_LAUNCH((region_rows_kernel<E, true>), grid, dim3(256), 0, s, ps, pd, r, chunks, dense_ne);
-        else         DSC_LAUNCH((region_rows_kernel<E, false>), grid, dim3(256), 0, s, ps, pd, r, chunks, dense_ne);
-    } else {
-        const dim3 grid = stream_grid(r.ne);
-        if (scatter) DSC_LAUNCH((region_flat_kernel<E, true>), grid, dim3(256), 0, s, ps, pd, r, dense_ne);
-        else         DSC_LAUNCH((region_flat_kernel<E, false>), grid, dim3(256), 0, s, ps, pd, r, dense_ne);
-    }
-}
-
-}  // namespace
-
-void dsc_launch_region_copy(const void *src, void *dst, int elem_bytes, const dsc_region &r, bool scatter, long long dense_ne,
-                            hipStream_t stream) {
-    if (r.ne <= 0) return;
-    // contiguous innermost rows whose ends fall on 16-byte boundaries (x[:, :60000], x[::2], a crop after irfft ...): move 16 bytes
-    // per lane instead of one element
-    const int V = 16 / elem_bytes;
-    if (V > 1 && r.stride[3] == 1 && dense_ne == r.ne && r.count[3] % V == 0 && r.base % V == 0 && (((size_t) src | (size_t) dst) & 15) == 0) {
-        bool ok = true;
-        for (int k = 0; k < 3; ++k) ok = ok && (r.count[k] == 1 || r.stride[k] % V == 0);
-        if (ok) {
-            dsc_region w = r;
-            w.base = r.base / V;
-            w.count[3] = r.count[3] / V;
-            for (int k = 0; k < 3; ++k) w.stride[k] = r.stride[k] / V;
-            w.ne = r.ne / V;
-            region_typed<b16>(src, dst, w, scatter, dense_ne / V, stream);
-            return;
-        }
-    }
-    switch (elem_bytes) {
-        case 4:  region_typed<unsigned int>(src, dst, r, scatter, dense_ne, stream); break;
-        case 8:  region_typed<unsigned long long>(src, dst, r, scatter, dense_ne, stream); break;
-        default: region_typed<b16>(src, dst, r, scatter, dense_ne, stream); break;
-    }
-}
-
-// ---- dsc_transpose of the last two axes (dsc.cpp:764-827 walks a stride iterator per element) ----
-namespace {
-
-template<typename E>
-__global__ void transpose_last2_kernel(const E *in, E *out, int rows, int cols, unsigned tiles_c, unsigned tiles_r) {
-    __shared__ E tile[32][33];
-    const unsigned long long blk = blockIdx.x;
-    const unsigned long long per = (unsigned long long) tiles_c * tiles_r;
-    const unsigned long long b = blk / per;
-    const unsigned rem = (unsigned) (blk - b * per);
-    const unsigned tr = rem / tiles_c, tc = rem - tr * tiles_c;
-    const E *src = in + b * (unsigned long long) rows * cols;
-    E *dst = out + b * (unsigned long long) rows * cols;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;              // 32 x 8 threads
-    for (int k = ty; k < 32; k += 8) {
-        const int r = tr * 32 + k, c = tc * 32 + tx;
-        if (r < rows && c < cols) tile[k][tx] = src[(long long) r * cols + c];
-    }
-    __syncthreads();
-    for (int k = ty; k < 32; k += 8) {
-        const int c = tc * 32 + k, r = tr * 32 + tx;
-        if (r < rows && c < cols) dst[(long long) c * rows + r] = tile[tx][k];
-    }
-}
-
-template<typename E>
-void transpose_typed(const void *in, void *out, long long batch, int rows, int cols, hipStream_t s) {
-    const unsigned tiles_c = (cols + 31) / 32, tiles_r = (rows + 31) / 32;
-    const unsigned long long blocks = (unsigned long long) batch * tiles_c * tiles_r;
-    DSC_LAUNCH((transpose_last2_kernel<E>), dim3((unsigned) blocks), dim3(256), 0, s, (const E *) in, (E *) out, rows, cols, tiles_c,
-                       tiles_r);
-}
-
-}  // namespace
-
-// ---- any permutation that moves the LAST axis (dsc_transpose with the reversed default, (2, 0, 1), ...): the plane spanned by the
-// input's last axis (c, stride 1 in the input) and the input axis that becomes the output's last axis (a, stride 1 in the output) is
-// transposed in 32 x 32 LDS tiles, both sides coalesced; the remaining (at most two) axes are a batch with their own strides.
-namespace {
-
-struct tr_plan {
-    int na, nc;                 // extents along a and c
-    long long sa_in, sc_out;    // input stride of a, output stride of c (elements)
-    int nb0, nb1;               // batch extents
-    long long b0_in, b0_out, b1_in, b1_out;
-};
-
-template<typename E>
-__global__ void transpose_plane_kernel(const E *in, E *out, tr_plan p, unsigned tiles_a, unsigned tiles_c) {
-    __shared__ E tile[32][33];
-    unsigned long long blk = blockIdx.x;
-    const unsigned tc = (unsigned) (blk % tiles_c); blk /= tiles_c;
-    const unsigned ta = (unsigned) (blk % tiles_a); blk /= tiles_a;
-    const unsigned i0 = (unsigned) (blk % (unsigned) p.nb0), i1 = (unsigned) (blk / (unsigned) p.nb0);
-    const E *src = in + i0 * p.b0_in + i1 * p.b1_in;
-    E *dst = out + i0 * p.b0_out + i1 * p.b1_out;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;              // 32 x 8 threads
-    for (int k = ty; k < 32; k += 8) {
-        const int a = ta * 32 + k, c = tc * 32 + tx;
-        if (a < p.na && c < p.nc) tile[k][tx] = src[a * p.sa_in + c];
-    }
-    __syncthreads();
-    for (int k = ty; k < 32; k += 8) {
-        const int c = tc * 32 + k, a = ta * 32 + tx;
-        if (a < p.na && c < p.nc) dst[c * p.sc_out + a] = tile[tx][k];
-    }
-}
-
-// The same plane transpose with 16-byte global accesses on BOTH sides (4- and 8-byte elements, V = 4 / 2 per access): a
-// (16 V) x (16 V) tile, 16 x 16 threads; a thread loads V packs (rows ty + 16 k, columns tx V ..) and stores V packs (output
-// rows ty + 16 k, elements tx V ..) gathered from V tile rows.  The 32 x 32 tiles move 128 bytes per row segment in f32
-// (41-49 % of the roofline for [256, 512, 1024]); this form moves 256.  Needs na, nc, sa_in, sc_out and the batch strides to
-// be multiples of V and 16-byte aligned bases: then a pack is never cut by the edge of the tensor.
-template<typename E>
-__global__ __launch_bounds__(256) void transpose_plane_vec_kernel(const E *in, E *out, tr_plan p, unsigned tiles_a, unsigned tiles_c) {
-    constexpr int V = 16 / (int) sizeof(E), TD = 16 * V;
-    __shared__ E tile[TD][TD + 1];
-    unsigned long long blk = blockIdx.x;
-    const unsigned tc = (unsigned) (blk % tiles_c); blk /= tiles_c;
-    const unsigned ta = (unsigned) (blk % tiles_a); blk /= tiles_a;
-    const unsigned i0 = (unsigned) (blk % (unsigned) p.nb0), i1 = (unsigned) (blk / (unsigned) p.nb0);
-    const E *src = in + i0 * p.b0_in + i1 * p.b1_in;
-    E *dst = out + i0 * p.b0_out + i1 * p.b1_out;
-    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-        const int la = ty + 16 * k, a = ta * TD + la, c = tc * TD + tx * V;
-        if (a < p.na && c < p.nc) {
-            const packed<E, V> q = *(const packed<E, V> *) (src + a * p.sa_in + c);
-#pragma unroll
-            for (int j = 0; j < V; ++j) tile[la][tx * V + j] = q.e[j];
-        }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-        const int lc = ty + 16 * k, c = tc * TD + lc, a = ta * TD + tx * V;
-        if (a < p.na && c < p.nc) {
-            packed<E, V> q;
-#pragma unroll
-            for (int j = 0; j < V; ++j) q.e[j] = tile[tx * V + j][lc];
-            *(packed<E, V> *) (dst + c * p.sc_out + a) = q;
-        }
-    }
-}
-
-template<typename E>
-bool transpose_plane_vec(const void *in, void *out, const tr_plan &p, hipStream_t s) {
-    constexpr int V = 16 / (int) sizeof(E), TD = 16 * V;
-    if (V == 1 || !aligned_to(in, 16) || !aligned_to(out, 16)) return false;
-    const long long must[] = {p.na, p.nc, p.sa_in, p.sc_out, p.nb0 > 1 ? p.b0_in : 0, p.nb0 > 1 ? p.b0_out : 0, p.nb1 > 1 ? p.b1_in : 0,
-                              p.nb1 > 1 ? p.b1_out : 0};
-    for (long long m : must) if (m % V != 0) return false;
-    const unsigned tiles_a = (p.na + TD - 1) / TD, tiles_c = (p.nc + TD - 1) / TD;
-    const unsigned long long blocks = (unsigned long long) tiles_a * tiles_c * p.nb0 * p.nb1;
-    if (blocks == 0 || blocks > 0x7fffffffull) return false;
-    DSC_LAUNCH((transpose_plane_vec_kernel<E>), dim3((unsigned) blocks), dim3(256), 0, s, (const E *) in, (E *) out, p, tiles_a, tiles_c);
-    return true;
-}
-
-template<typename E>
-void transpose_plane_typed(const void *in, void *out, const tr_plan &p, hipStream_t s) {
-    if (transpose_plane_vec<E>(in, out, p, s)) return;
-    const unsigned tiles_a = (p.na + 31) / 32, tiles_c = (p.nc + 31) / 32;
-    const unsigned long long blocks = (unsigned long long) tiles_a * tiles_c * p.nb0 * p.nb1;
-    DSC_LAUNCH((transpose_plane_kernel<E>), dim3((unsigned) blocks), dim3(256), 0, s, (const E *) in, (E *) out, p, tiles_a, tiles_c);
-}
-
-}  // namespace
-
-// shape / in_stride: the INPUT's extents and element strides per axis (n_dim <= 4, dense); perm: result axis i = input axis perm[i],
-// with perm[n_dim - 1] != n_dim - 1.  Returns false if the launch would not fit (the caller keeps the strided copy).
-bool dsc_launch_transpose_moving_last(const void *in, void *out, int elem_bytes, int n_dim, const int *shape, const int *in_stride, const int *perm,
-                                      hipStream_t stream) {
-    long long out_stride[4] = {1, 1, 1, 1};
-    for (int i = n_dim - 2; i >= 0; --i) out_stride[i] = out_stride[i + 1] * shape[perm[i + 1]];
-    const int a_axis = perm[n_dim - 1], c_axis = n_dim - 1;            // input axes of the tile plane
-    tr_plan p;
-    p.na = shape[a_axis]; p.nc = shape[c_axis];
-    p.sa_in = in_stride[a_axis];
-    p.sc_out = 1;
-    p.nb0 = p.nb1 = 1; p.b0_in = p.b0_out = p.b1_in = p.b1_out = 0;
-    int nb = 0;
-    for (int i = 0; i < n_dim; ++i) {                                   // result axis i <- input axis perm[i]
-        const int ax = perm[i];
-        if (ax == c_axis) { p.sc_out = out_stride[i]; continue; }
-        if (ax == a_axis) continue;
-        if (nb == 0) { p.nb0 = shape[ax]; p.b0_in = in_stride[ax]; p.b0_out = out_stride[i]; }
-        else         { p.nb1 = shape[ax]; p.b1_in = in_stride[ax]; p.b1_out = out_stride[i]; }
-        ++nb;
-    }
-    const unsigned long long blocks = (unsigned long long) ((p.na + 31) / 32) * ((p.nc + 31) / 32) * p.nb0 * p.nb1;
-    if (blocks == 0) return true;
-    if (blocks > 0x7fffffffull) return false;
-    switch (elem_bytes) {
-        case 4:  transpose_plane_typed<unsigned int>(in, out, p, stream); break;
-        case 8:  transpose_plane_typed<unsigned long long>(in, out, p, stream); break;
-        default: transpose_plane_typed<b16>(in, out, p, stream); break;
-    }
-    return true;
-}
-
-void dsc_launch_transpose_last2(const void *in, void *out, int elem_bytes, long long batch, int rows, int cols, hipStream_t stream) {
-    if (batch <= 0 || rows <= 0 || cols <= 0) return;
-    if (elem_bytes < 16 && batch < (1LL << 31)) {                       // [batch][rows][cols] -> [batch][cols][rows] as a plane plan
-        tr_plan p;
-        p.na = rows; p.nc = cols; p.sa_in = cols; p.sc_out = rows;
-        p.nb0 = (int) batch; p.b0_in = p.b0_out = (long long) rows * cols;
-        p.nb1 = 1; p.b1_in = p.b1_out = 0;
-        if (elem_bytes == 4 ? transpose_plane_vec<unsigned int>(in, out, p, stream) : transpose_plane_vec<unsigned long long>(in, out, p, stream)) return;
-    }
-    switch (elem_bytes) {
-        case 4:  transpose_typed<unsigned int>(in, out, batch, rows, cols, stream); break;
-        case 8:  transpose_typed<unsigned long long>(in, out, batch, rows, cols, stream); break;
-        default: transpose_typed<b16>(in, out, batch, rows, cols, stream); break;
-    }
+    with_dtype(dtype, [&](auto t) {
+        with_index<5>("elementwise.hip", "binary op", op, [&](auto opc) {
+            using T = decltype(t);
+            binary_op<T, decltype(opc)::value>((const T *) a, (const T *) b, (T *) out, g, stream);
+        });
+    });
 }

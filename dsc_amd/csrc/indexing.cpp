@@ -4,7 +4,7 @@
 // Behavioural contract: dsc/src/dsc.cpp:764-1169 and :2262-2340 — which selections are accepted, what they select, the
 // shape of the result, what is refused.  Structure here: every entry point turns its variadic arguments into a list of
 // per-axis picks (`pick`: first element, count, step), `choose()` folds the picks into ONE strided region of the tensor
-// (dsc_region), and a single gather / scatter launch moves it (elementwise.hip) — where the reference walks the selection
+// (dsc_region), and a single gather / scatter launch moves it (layout.hip) — where the reference walks the selection
 // element by element with dsc_slice_iterator (dsc_iter.h:125-190).  The README's `[:output_length]` crop after dsc_irfft
 // and the placement of a block into a zero-padded buffer (README.md:113-135) therefore never leave HBM.
 #include "dsc_internal.h"

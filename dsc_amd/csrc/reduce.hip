@@ -23,14 +23,9 @@
 // the complex min never takes one.  The sequential kernels apply the predicate as is; partial results
 // carry "contains a NaN", which makes the ordered combination exact (a segment with a NaN wipes what
 // came before it); the tree kernel finds the last NaN of the row first.
-#include "kernels.h"
-
-#include <hip/hip_runtime.h>
-#include <type_traits>
+#include "stream_common.h"
 
 namespace {
-
-template<typename T> struct alignas(2 * sizeof(T)) cx { T x, y; };
 
 template<typename R, bool CPLX> struct acc_t { R r, i; int idx; };
 
@@ -314,18 +309,9 @@ void launch_op(const void *x, void *out, long long outer, int axis_n, long long 
         const long long n_out = outer * inner;
         long long blocks = (n_out / (packs ? VP : 1) + 255) / 256;
         if (blocks > 256 * 8) blocks = 256 * 8;
-        if (packs) DSC_LAUNCH((reduce_seq_kernel<R, CPLX, OP, VP>), dim3((unsigned) blocks), dim3(256), 0, s, x, out, outer, axis_n, inner);
-        else       DSC_LAUNCH((reduce_seq_kernel<R, CPLX, OP, 1>), dim3((unsigned) blocks), dim3(256), 0, s, x, out, outer, axis_n, inner);
-    }
-}
-
-template<typename R, bool CPLX>
-void launch_typed(const void *x, void *out, int op, long long outer, int axis_n, long long inner, void *ws, size_t wsb, hipStream_t s) {
-    switch (op) {
-        case 0: launch_op<R, CPLX, 0>(x, out, outer, axis_n, inner, ws, wsb, s); break;
-        case 1: launch_op<R, CPLX, 1>(x, out, outer, axis_n, inner, ws, wsb, s); break;
-        case 2: launch_op<R, CPLX, 2>(x, out, outer, axis_n, inner, ws, wsb, s); break;
-        default: launch_op<R, CPLX, 3>(x, out, outer, axis_n, inner, ws, wsb, s); break;
+        with_bool(packs, [&](auto pk) {
+            DSC_LAUNCH((reduce_seq_kernel<R, CPLX, OP, decltype(pk)::value ? VP : 1>), dim3((unsigned) blocks), dim3(256), 0, s, x, out, outer, axis_n, inner);
+        });
     }
 }
 
@@ -334,10 +320,10 @@ void launch_typed(const void *x, void *out, int op, long long outer, int axis_n,
 void dsc_launch_reduce(const void *x, void *out, int dtype, int op, long long outer, int axis_n, long long inner,
                        void *workspace, size_t workspace_bytes, hipStream_t stream) {
     if (outer * inner <= 0) return;
-    switch (dtype) {
-        case 0: launch_typed<float, false>(x, out, op, outer, axis_n, inner, workspace, workspace_bytes, stream); break;
-        case 1: launch_typed<double, false>(x, out, op, outer, axis_n, inner, workspace, workspace_bytes, stream); break;
-        case 2: launch_typed<float, true>(x, out, op, outer, axis_n, inner, workspace, workspace_bytes, stream); break;
-        default: launch_typed<double, true>(x, out, op, outer, axis_n, inner, workspace, workspace_bytes, stream); break;
-    }
+    with_dtype(dtype, [&](auto t) {
+        with_index<4>("reduce.hip", "reduction", op, [&](auto opc) {
+            using E = elem<decltype(t)>;
+            launch_op<typename E::real, E::cplx, decltype(opc)::value>(x, out, outer, axis_n, inner, workspace, workspace_bytes, stream);
+        });
+    });
 }

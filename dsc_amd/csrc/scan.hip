@@ -18,18 +18,13 @@
 //   inner > 1    scan_cols_kernel: one thread per (outer, inner) element walks the axis; neighbouring threads read neighbouring
 //                addresses.  cumsum in numpy's own left-to-right order.  The axis is not segmented: few columns are slow.
 //   diff         scan_diff_kernel: out[o][j][i] = x[o][j + 1][i] - x[o][j][i], flat over the output.
-#include "dispatch.h"
-
-#include <hip/hip_runtime.h>
-#include <type_traits>
+#include "stream_common.h"
 
 namespace {
 
 constexpr int kThreads = 1024, kWaves = kThreads / 64;
 constexpr double kTwoPi = 6.283185307179586, kPi = 3.141592653589793;
 
-template<typename T> struct alignas(2 * sizeof(T)) cx { T x, y; };
-template<typename E, int V> struct alignas(sizeof(E) * V) pack { E e[V]; };
 
 template<typename S> struct is_cx : std::false_type {};
 template<typename T> struct is_cx<cx<T>> : std::true_type {};
@@ -86,7 +81,7 @@ template<typename R> __device__ __forceinline__ R unwrap_out(R a, int K) {
     return (R) fma(-(double) K, kTwoPi, (double) a);
 }
 
-template<typename In, int V, int U> struct chunk_regs { pack<In, V> p[U]; In halo; };
+template<typename In, int V, int U> struct chunk_regs { packed<In, V> p[U]; In halo; };
 
 // the calling thread's packs of the chunk that starts at position j0 of the row xrow; positions from jend on do not belong to the
 // segment.  Pack u of lane l of wave w is pack (w U + u) 64 + l of the chunk: a wave owns U 64 consecutive packs.
@@ -97,7 +92,7 @@ __device__ __forceinline__ void load_chunk(const In *__restrict__ xrow, long lon
     for (int u = 0; u < U; ++u) {
         const long long j = j0 + (long long) (((w * U + u) * 64 + lane) * V);
         if (j < jend) {
-            r.p[u] = *(const pack<In, V> *) (xrow + j);
+            r.p[u] = *(const packed<In, V> *) (xrow + j);
         } else {
 #pragma unroll
             for (int k = 0; k < V; ++k) r.p[u].e[k] = s_zero<In>();
@@ -224,14 +219,14 @@ __global__ __launch_bounds__(kThreads) void scan_seg_kernel(const In *__restrict
             for (int u = 0; u < U; ++u) {
                 if (j[u] < g.end) {
                     const S base = s_add(s_add(before, run[u]), excl[u]);
-                    pack<Out, V> o;
+                    packed<Out, V> o;
 #pragma unroll
                     for (int k = 0; k < V; ++k) {
                         const S sc = s_add(base, p[u][k]);
                         if constexpr (OP == 0) o.e[k] = sc;
                         else                   o.e[k] = unwrap_out<Out>(a[u][k], sc);
                     }
-                    *(pack<Out, V> *) (orow + j[u]) = o;
+                    *(packed<Out, V> *) (orow + j[u]) = o;
                 }
             }
         } else {
@@ -285,15 +280,13 @@ __global__ void scan_diff_kernel(const E *__restrict__ x, E *__restrict__ out, u
     for (unsigned p = blockIdx.x * blockDim.x + threadIdx.x; p < n_packs; p += gridDim.x * blockDim.x) {
         const unsigned o = p * V, q = o / row_len;
         const long long i = (long long) o + (long long) q * inner;
-        const pack<E, V> lo = *(const pack<E, V> *) (x + i), hi = *(const pack<E, V> *) (x + i + inner);
-        pack<E, V> r;
+        const packed<E, V> lo = *(const packed<E, V> *) (x + i), hi = *(const packed<E, V> *) (x + i + inner);
+        packed<E, V> r;
 #pragma unroll
         for (int k = 0; k < V; ++k) r.e[k] = s_sub(hi.e[k], lo.e[k]);
-        *(pack<E, V> *) (out + o) = r;
+        *(packed<E, V> *) (out + o) = r;
     }
 }
-
-bool aligned_to(const void *p, size_t a) { return ((size_t) p & (a - 1)) == 0; }
 
 template<int OP, typename In, bool TOTALS>
 void launch_seg(const In *x, typename scan_types<OP, In>::Out *out, const typename scan_types<OP, In>::S *carry_in,
@@ -303,8 +296,9 @@ void launch_seg(const In *x, typename scan_types<OP, In>::Out *out, const typena
     const bool packs = VP > 1 && n % VP == 0 && tile_len % VP == 0 && aligned_to(x, 16) && aligned_to(out, sizeof(Out) * VP);
     const long long cus = dsc_cu_count();
     const dim3 grid((unsigned) (n_seg < cus ? n_seg : cus));
-    if (packs) DSC_LAUNCH((scan_seg_kernel<OP, In, VP, TOTALS>), grid, dim3(kThreads), 0, s, x, out, carry_in, totals, n_seg, n, tile_len, tiles_per_row);
-    else       DSC_LAUNCH((scan_seg_kernel<OP, In, 1, TOTALS>), grid, dim3(kThreads), 0, s, x, out, carry_in, totals, n_seg, n, tile_len, tiles_per_row);
+    with_bool(packs, [&](auto pk) {
+        DSC_LAUNCH((scan_seg_kernel<OP, In, decltype(pk)::value ? VP : 1, TOTALS>), grid, dim3(kThreads), 0, s, x, out, carry_in, totals, n_seg, n, tile_len, tiles_per_row);
+    });
 }
 
 template<int OP, typename In> constexpr int tile_len_of() { return kThreads * packs_per_thread<OP, In>() * (16 / (int) sizeof(In)); }
@@ -386,7 +380,8 @@ void dsc_launch_scan_diff(const void *x, void *out, int dtype, long long outer, 
         long long blocks = (n_packs + 255) / 256;
         if (blocks > 256 * 32) blocks = 256 * 32;
         const unsigned row_len = (unsigned) ((n - 1) * inner);
-        if (packs) DSC_LAUNCH((scan_diff_kernel<E, VP>), dim3((unsigned) blocks), dim3(256), 0, stream, (const E *) x, (E *) out, (unsigned) n_packs, row_len, (unsigned) inner);
-        else       DSC_LAUNCH((scan_diff_kernel<E, 1>), dim3((unsigned) blocks), dim3(256), 0, stream, (const E *) x, (E *) out, (unsigned) n_packs, row_len, (unsigned) inner);
+        with_bool(packs, [&](auto pk) {
+            DSC_LAUNCH((scan_diff_kernel<E, decltype(pk)::value ? VP : 1>), dim3((unsigned) blocks), dim3(256), 0, stream, (const E *) x, (E *) out, (unsigned) n_packs, row_len, (unsigned) inner);
+        });
     });
 }

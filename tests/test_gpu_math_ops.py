@@ -316,6 +316,51 @@ def test_ref_ops_power(dsc):
         assert _close(dsc.power(xd, s).numpy(), np.power(x, s).astype(dtype)) and _close((s ** xd).numpy(), (s ** x).astype(dtype))
 
 
+# ---- pow on every route of the binary launcher (the route tests of the other files run add, sub, mul and div)
+
+# (shape of a, shape of b): one pair per branch of dsc_launch_binary; unequal pairs run in both operand orders
+BINARY_ROUTES = (
+    ((6, 1000), (6, 1000)),              # equal shapes, 16 bytes per lane
+    ((5, 1001), (5, 1001)),              # equal shapes, odd count: one element per thread
+    ((8, 512), (512,)),                  # trailing operand, packed
+    ((3, 5), (5,)),                      # trailing operand, one element per thread
+    ((4, 1024), (1,)),                   # scalar, packed
+    ((3, 5), (1,)),                      # scalar, general kernel
+    ((12, 512), (12, 1)),                # leading (column) operand, packed
+    ((9, 2), (9, 1)),                    # a column too short for a pack
+    ((4, 3, 8, 64), (4, 1, 8, 1)),       # general broadcast, packed
+    ((4, 3, 8, 65), (4, 1, 8, 1)),       # general broadcast, one block per piece of a row
+    ((2, 3, 4, 6), (3, 1, 6)),           # general broadcast, flat
+)
+# the other operand of the two mixed-dtype cases, chosen so that the promotion (dsc_dtype.h:73-78) widens without rounding
+MIXED_WITH = {np.float32: np.complex64, np.float64: np.float32, np.complex64: np.complex128, np.complex128: np.float64}
+
+
+def _pow_operands(shape_a, shape_b, dtype_a, dtype_b, rng):
+    def draw(shape, dtype, re, im):
+        x = rng.uniform(*re, shape)
+        if np.dtype(dtype).kind == 'c':
+            x = x + 1j * rng.uniform(*im, shape)
+        return x.astype(dtype)
+    return draw(shape_a, dtype_a, (0.1, 4), (-2, 2)), draw(shape_b, dtype_b, (-3, 3), (-1, 1))
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_pow_on_every_binary_route(dsc, dtype):
+    rng = np.random.default_rng(16)
+    cases = [(sa, sb, dtype, dtype) for sa, sb in BINARY_ROUTES]
+    cases += [(sb, sa, dtype, dtype) for sa, sb in BINARY_ROUTES if sa != sb]
+    for shape in ((6, 1000), (5, 1001)):                     # promoted in registers; through the cast kernels
+        cases += [(shape, shape, dtype, MIXED_WITH[dtype]), (shape, shape, MIXED_WITH[dtype], dtype)]
+    for sa, sb, da, db in cases:
+        a, b = _pow_operands(sa, sb, da, db, rng)
+        out = np.result_type(da, db)
+        wide = np.complex128 if np.dtype(out).kind == 'c' else np.float64
+        want = np.power(a.astype(wide), b.astype(wide)).astype(out)
+        got = dsc.power(dsc.from_numpy(a), dsc.from_numpy(b)).numpy()
+        assert_matches(got, want, *tolerance('pow', out), what=f'pow {np.dtype(da)}{sa} ** {np.dtype(db)}{sb}')
+
+
 def test_ref_ops_unary(dsc):
     rng = np.random.default_rng(12)
     for dtype in DTYPES:

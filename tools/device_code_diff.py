@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Compare the kernels of two device assembly listings (hipcc ... --cuda-device-only -S).
 
-usage: device_code_diff.py A.s B.s
+usage: device_code_diff.py A.s B.s [B2.s ...]
+
+Several B listings count as one: a file of A that was split (each is read on its own; a concatenation would run the tail of one
+listing into the first kernel of the next).
 
 A kernel is its code, from the symbol's label to its .Lfunc_end, plus its .amdhsa_kernel descriptor block.  The labels that
 carry the function's number (.LBB<n>_, .LJTI<n>_, .Ltmp<n>, .Lfunc_end<n>) are rewritten to a neutral form first: they
@@ -27,9 +30,11 @@ def kernels(path):
 
 
 def main():
-    if len(sys.argv) != 3:
+    if len(sys.argv) < 3:
         sys.exit(__doc__)
-    a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+    a, b = kernels(sys.argv[1]), {}
+    for path in sys.argv[2:]:
+        b.update(kernels(path))
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     differing = sorted(k for k in set(a) & set(b) if a[k] != b[k] or a[k][0] is None)
     for title, names in (("only in A", only_a), ("only in B", only_b), ("differing", differing)):

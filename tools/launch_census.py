@@ -11,7 +11,11 @@
           operators (stft, istft, convolve, correlate, hilbert, envelope, fft2, cumsum, unwrap, diff, resample_poly): one small call per
           route, the composed routes with their DSC_NO_..._FUSED switch set around the call, scan_rows / scan_tiles through
           DSC_SCAN_ROUTE, and the chunked branches of stft, istft, convolve, correlate, hilbert and envelope at n = 1024 in a second
-          context with 64 KiB of scratch, three chunks each.  Prints one line per call, 'CALL ... <dsc.last_fft_path()>'.
+          context with 64 KiB of scratch, three chunks each.  Then the streaming files (elementwise, layout, reduce): one small call per
+          branch of every launcher in them x the four dtypes — the five binary operators on every broadcast route and with operands of
+          two dtypes, the unary functions, casts and arange at aligned, odd and 8-bytes-off-alignment counts, the four reductions on
+          every kernel, slices (get and set) and transposes per element size.  Prints one line per call,
+          'CALL ... <dsc.last_fft_path()>'.
 --compare the kernel-trace CSVs below the two directories in dispatch order: the same sequence of (Kernel_Name, Grid_Size, Workgroup_Size,
           LDS_Block_Size), and the same paths.txt.  Exits 1 on a difference.
 """
@@ -70,6 +74,10 @@ def run():
         for T in (100, 260, 4096):
             call('resample_poly', lambda x: dsc.resample_poly(x, 3, 2), (2, T), rdt)
     operators(dsc, np, call)
+    dsc.synchronize()
+    dsc.shutdown()
+    dsc.init(2 << 30, 256 << 20)
+    streaming(dsc, np)
     dsc.synchronize()
 
 
@@ -137,6 +145,102 @@ def operators(dsc, np, call):
         dsc.init(256 << 20, (64 << 10) * np.dtype(dt).itemsize // 4)
         with switch('DSC_NO_STFT_FUSED'), switch('DSC_NO_CONV_FUSED'), switch('DSC_NO_HILBERT_FUSED'), switch('DSC_CONV_N', '1024'):
             signal_ops(dt, 4864, [(5, 4, 513), (1, 20, 513)], 7000, 11)
+
+
+def streaming(dsc, np):
+    import ctypes
+    from dsc_amd import _bindings as B
+    from dsc_amd.context import _get_ctx
+    from dsc_amd.dtype import NP_TO_DTYPE
+    DTYPES = (np.float32, np.float64, np.complex64, np.complex128)
+    BINARY = ('add', 'sub', 'mul', 'true_div', 'power')
+    UNARY = ('absolute', 'angle', 'conj', 'real', 'imag', 'cos', 'sin', 'sinc', 'logn', 'log2', 'log10', 'exp', 'sqrt', 'i0', 'clip')
+
+    def ones(shape, dt):
+        return dsc.from_numpy(np.ones(shape, dtype=dt))
+
+    def call(what, fn, shape, dt, *note):                           # as run()'s, with notes in place of keyword arguments
+        x = ones(shape, dt)
+        y = fn(x)
+        print('CALL', what, np.dtype(dt).name, shape, *note, flush=True)
+        del x, y
+
+    @contextlib.contextmanager
+    def offset_view(shape, dt):
+        """ones in a view 8 bytes off the 16-byte alignment of the packed kernels, as tests/test_gpu_math_ops.py::_Offset"""
+        x = np.ones(shape, dtype=dt)
+        raw = B.dsc_device_alloc(_get_ctx(), x.nbytes + 256)
+        view = dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), raw + 8, x.nbytes, x.ndim, (ctypes.c_int * x.ndim)(*shape), NP_TO_DTYPE[x.dtype].value))
+        B.dsc_copy_from_host(_get_ctx(), view._c_ptr, x.ctypes.data, x.nbytes)
+        try:
+            yield view
+        finally:
+            del view
+            dsc.synchronize()
+            B.dsc_device_free(_get_ctx(), raw)
+
+    def unary_and_cast(x, dt, what):
+        for name in UNARY:
+            if name == 'i0' and np.dtype(dt).kind == 'c':
+                continue
+            y = dsc.clip(x, 0.5, 2.0) if name == 'clip' else getattr(dsc, name)(x)
+            print('CALL', name, what, flush=True)
+            del y
+        for to in DTYPES:
+            if to != dt:
+                y = x.cast(NP_TO_DTYPE[np.dtype(to)])
+                print('CALL cast', what, np.dtype(to).name, flush=True)
+                del y
+
+    # (shape of a, shape of b) per branch of dsc_launch_binary, the unequal ones in both operand orders
+    pairs = [((6, 1000), (6, 1000)), ((5, 1001), (5, 1001)), ((8, 512), (512,)), ((3, 5), (5,)), ((4, 1024), (1,)), ((3, 5), (1,)),
+             ((12, 512), (12, 1)), ((9, 2), (9, 1)), ((4, 3, 8, 64), (4, 1, 8, 1)), ((4, 3, 8, 65), (4, 1, 8, 1)), ((2, 3, 4, 6), (3, 1, 6))]
+    pairs += [(sb, sa) for sa, sb in pairs if sa != sb]
+    for dt in DTYPES:
+        for name in BINARY:
+            for sa, sb in pairs:
+                call(name, lambda x: getattr(dsc, name)(x, ones(sb, dt)), sa, dt, sb)
+            for other in DTYPES:                                    # two dtypes: promoted in registers (even count), through the casts (odd)
+                if other != dt:
+                    for shape in ((6, 1000), (5, 1001)):
+                        call(name, lambda x: getattr(dsc, name)(x, ones(shape, other)), shape, dt, np.dtype(other).name)
+        for n in (4096, 4099, 3):
+            unary_and_cast(ones(n, dt), dt, '%s %d' % (np.dtype(dt).name, n))
+        with offset_view((1001,), dt) as view:
+            unary_and_cast(view, dt, '%s 1001 + 8 bytes' % np.dtype(dt).name)
+        for sa, sb in (((8, 512), (512,)), ((4, 3, 8, 65), (4, 1, 8, 1)), ((2, 3, 4, 6), (3, 1, 6))):
+            with offset_view(sa, dt) as view:                       # the large operand off alignment: no packs on the trailing and general routes
+                for name in BINARY:
+                    y, z = getattr(dsc, name)(view, ones(sb, dt)), getattr(dsc, name)(ones(sb, dt), view)
+                    print('CALL', name, np.dtype(dt).name, sa, sb, '+ 8 bytes, both orders', flush=True)
+                    del y, z
+        for n in (1, 4099):
+            y = dsc.arange(n, NP_TO_DTYPE[np.dtype(dt)])
+            print('CALL arange', np.dtype(dt).name, n, flush=True)
+            del y
+        for name in ('sum', 'mean', 'max', 'min'):                  # row, sequential, wave, segmented, sequential in packs
+            for shape, axis in (((37, 5000), 1), ((37, 5000), 0), ((2048, 1024), 1), ((3000, 700), 0), ((2, 524288), 0)):
+                call(name, lambda x: getattr(dsc, name)(x, axis=axis), shape, dt, axis)
+        for key in ((slice(None), slice(None, 60)), (slice(None), slice(1, 62)), (slice(None), slice(None, 600)), (slice(None), slice(None, None, 2)),
+                    (slice(None), slice(None, 512))):               # flat (widened where the element allows), flat, rows, strided, widened to 16 bytes
+            call('get_slice', lambda x: x[key], (8, 1024), dt, key)
+            call('set_slice', lambda x: x.__setitem__(key, 2.0), (8, 1024), dt, key, 'scalar')
+            call('set_slice', lambda x: x.__setitem__(key, x[key]), (8, 1024), dt, key, 'tensor')
+        for shape in ((64, 128), (33, 50)):
+            call('transpose', dsc.transpose, shape, dt)
+        for n in (1000, 1001):                                      # scan.hip: 16-byte packs and one element per pack
+            call('cumsum', dsc.cumsum, (3, n), dt)
+            call('diff', lambda x: dsc.diff(x, axis=0), (30, n), dt)
+            turns = ('unwrap', dsc.unwrap) if np.dtype(dt).kind == 'f' else ('phase', dsc.phase)
+            call(turns[0], turns[1], (3, n), dt)
+            call('cumsum', lambda x: dsc.cumsum(x, axis=0), (30, n), dt)
+            call(turns[0], lambda x: turns[1](x, axis=0), (30, n), dt)
+            with switch('DSC_SCAN_ROUTE', 'tiles'):                 # the totals pass (20021: no packs); 32768: the totals of a row fill whole packs
+                for m in (20 * n + n % 2, 32768):
+                    call('cumsum', dsc.cumsum, (3, m), dt, 'tiles')
+                    call(turns[0], turns[1], (3, m), dt, 'tiles')
+        for shape in ((8, 16, 32), (3, 5, 7)):
+            call('transpose', lambda x: dsc.transpose(x, (2, 0, 1)), shape, dt)
 
 
 def trace(d):
