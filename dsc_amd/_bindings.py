@@ -187,6 +187,11 @@ dsc_cumsum = _sig('dsc_cumsum', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_
 dsc_diff = _sig('dsc_diff', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
 dsc_unwrap = _sig('dsc_unwrap', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
 dsc_phase = _sig('dsc_phase', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int)
+dsc_roll = _sig('dsc_roll', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, POINTER(c_int), POINTER(c_int))
+dsc_flip = _sig('dsc_flip', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, POINTER(c_int))
+dsc_fftshift = _sig('dsc_fftshift', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, POINTER(c_int))
+dsc_ifftshift = _sig('dsc_ifftshift', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, POINTER(c_int))
+dsc_pad = _sig('dsc_pad', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, POINTER(c_int), c_int, c_double, c_double)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

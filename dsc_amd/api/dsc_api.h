@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope`, `dsc::upfirdn / resample_poly / decimate / firwin` and `dsc::cumsum / diff / unwrap / phase`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope`, `dsc::upfirdn / resample_poly / decimate / firwin`, `dsc::cumsum / diff / unwrap / phase` and `dsc::roll / flip / fftshift / ifftshift / pad`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -289,6 +289,41 @@ template<typename T>
 static inline tensor<T> unwrap(const tensor<T> &x, int axis = -1) noexcept { return dsc_unwrap(ctx, x.x_, nullptr, axis); }
 template<typename T>
 static inline tensor<T> phase(const tensor<T> &z, int axis = -1) noexcept { return dsc_phase(ctx, z.x_, nullptr, axis); }
+
+// Section J of dsc_mi355x.h: index maps along axes (numpy.roll / flip / fft.fftshift / fft.ifftshift / pad), bit-identical to numpy.
+// roll(x, shift) rolls the flattened tensor, roll(x, shift, axis) one axis, roll(x, {shifts}, {axes}) several; flip / fftshift /
+// ifftshift(x) take every axis, (x, {axes}) the listed ones; pad(x, {before, after, ...}, mode, value): one pair per axis of x, mode
+// 0 constant, 1 edge, 2 reflect, 3 symmetric, 4 wrap, the constant as (re, im)
+template<typename T>
+static inline tensor<T> roll(const tensor<T> &x, int shift) noexcept { return dsc_roll(ctx, x.x_, nullptr, 0, &shift, nullptr); }
+template<typename T>
+static inline tensor<T> roll(const tensor<T> &x, int shift, int axis) noexcept { return dsc_roll(ctx, x.x_, nullptr, 1, &shift, &axis); }
+template<typename T>
+static inline tensor<T> roll(const tensor<T> &x, std::initializer_list<int> shifts, std::initializer_list<int> axes) noexcept {
+    const std::vector<int> s(shifts), a(axes);
+    return dsc_roll(ctx, x.x_, nullptr, (int) (s.size() < a.size() ? s.size() : a.size()), s.data(), a.data());
+}
+template<typename T>
+static inline tensor<T> flip(const tensor<T> &x, std::initializer_list<int> axes = {}) noexcept {
+    const std::vector<int> a(axes);
+    return dsc_flip(ctx, x.x_, nullptr, (int) a.size(), a.data());
+}
+template<typename T>
+static inline tensor<T> fftshift(const tensor<T> &x, std::initializer_list<int> axes = {}) noexcept {
+    const std::vector<int> a(axes);
+    return dsc_fftshift(ctx, x.x_, nullptr, (int) a.size(), a.data());
+}
+template<typename T>
+static inline tensor<T> ifftshift(const tensor<T> &x, std::initializer_list<int> axes = {}) noexcept {
+    const std::vector<int> a(axes);
+    return dsc_ifftshift(ctx, x.x_, nullptr, (int) a.size(), a.data());
+}
+template<typename T>
+static inline tensor<T> pad(const tensor<T> &x, std::initializer_list<int> pad_width, int mode = 0, double value_re = 0, double value_im = 0) noexcept {
+    std::vector<int> w(pad_width);
+    w.resize(2 * (size_t) x.ndim(), 0);
+    return dsc_pad(ctx, x.x_, nullptr, w.data(), mode, value_re, value_im);
+}
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

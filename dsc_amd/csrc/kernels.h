@@ -301,6 +301,15 @@ struct dsc_region {
 void dsc_launch_region_copy(const void *src, void *dst, int elem_bytes, const dsc_region &r, bool scatter, long long dense_ne,
                             hipStream_t stream);
 
+// ---- index maps along axes (dsc_roll / dsc_flip / dsc_fftshift / dsc_ifftshift / dsc_pad, remap.cpp) ------
+// dsc_axis_map and dsc_remap, the plan: out[j0, j1, j2, j3] = x[m0(j0), m1(j1), m2(j2), m3(j3)] or the plan's constant.  Declared in a
+// header of their own with the integer arithmetic on them (dsc_map_index, dsc_remap_merge, dsc_remap_route), which a stand-alone host
+// program can include.
+#include "remap_plan.h"
+// One pass of a MERGED plan (remap.hip) on the given route, which the caller took from dsc_remap_route or weakened to DSC_REMAP_ELEMS;
+// the plan travels as a kernel argument.  x and out dense, of elem_bytes-byte elements, not overlapping.
+void dsc_launch_remap(const void *x, void *out, int elem_bytes, const dsc_remap &plan, int route, hipStream_t stream);
+
 // out[b][c][r] = in[b][r][c] for `batch` matrices of rows x cols elements (32 x 32 tiles through LDS: both sides coalesced)
 void dsc_launch_transpose_last2(const void *in, void *out, int elem_bytes, long long batch, int rows, int cols, hipStream_t stream);
 // any permutation that moves the last axis (n_dim <= 4, dense input): tiled through LDS, coalesced on both sides

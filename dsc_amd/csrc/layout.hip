@@ -1,23 +1,7 @@
 // layout.hip — kernels that move elements without looking at them: the slice gather / scatter of dsc_tensor_get_slice / set_slice
 // and dsc_concat, and the three transposes (last two axes; any permutation that moves the last axis, scalar and 16-byte forms).
-// Elements are opaque 4-, 8- or 16-byte words (with_elem_bytes).
+// Elements are opaque 4-, 8- or 16-byte words (with_elem_bytes of stream_common.h).
 #include "stream_common.h"
-
-namespace {
-
-struct alignas(16) b16 { unsigned long long a, b; };
-
-// element size in bytes -> an unsigned type of that size
-template<typename F> void with_elem_bytes(int elem_bytes, F f) {
-    switch (elem_bytes) {
-        case 4:  return f((unsigned int) 0);
-        case 8:  return f((unsigned long long) 0);
-        case 16: return f(b16{});
-    }
-    no_kernel("layout.hip", "element size", elem_bytes);
-}
-
-}  // namespace
 
 // ---- slice regions: dsc_tensor_get_slice / set_slice (dsc.cpp:868-1169) ---------------------
 // The reference walks a dsc_slice_iterator (dsc_iter.h:125-190) per element; here a block owns a piece of

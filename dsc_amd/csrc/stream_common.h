@@ -1,5 +1,6 @@
-// stream_common.h — what the streaming kernel files (elementwise.hip, layout.hip, reduce.hip, scan.hip) share: the element types
-// behind the four dtype codes, the 16-byte pack, the capped streaming grid and the dtype table of the dispatch.h idiom.
+// stream_common.h — what the streaming kernel files (elementwise.hip, layout.hip, remap.hip, reduce.hip, scan.hip) share: the element
+// types behind the four dtype codes, the 16-byte pack, the capped streaming grid and the dtype and element-size tables of the dispatch.h
+// idiom.
 // Everything sits in an anonymous namespace: cx and packed appear in kernel signatures, and each file keeps its own internal kernels.
 #pragma once
 
@@ -37,6 +38,17 @@ template<typename F> void with_dtype(int dtype, F f) {
         case 3: return f(cx<double>{});
     }
     no_kernel("stream_common.h", "dtype", dtype);
+}
+
+// element size in bytes -> an unsigned type of that size: the kernels that move elements without looking at them (layout.hip, remap.hip)
+struct alignas(16) b16 { unsigned long long a, b; };
+template<typename F> void with_elem_bytes(int elem_bytes, F f) {
+    switch (elem_bytes) {
+        case 4:  return f((unsigned int) 0);
+        case 8:  return f((unsigned long long) 0);
+        case 16: return f(b16{});
+    }
+    no_kernel("stream_common.h", "element size", elem_bytes);
 }
 
 }  // namespace

@@ -462,6 +462,76 @@ def phase(z: Tensor, axis: int = -1, out: Union[Tensor, None] = None) -> Tensor:
     return _scan(B.dsc_phase, z, axis, out)
 
 
+# ---- index maps along axes (include/dsc_mi355x.h, Section J): numpy.roll / flip / fft.fftshift / fft.ifftshift / pad in one pass, bit-identical
+# to numpy.  Ints or tuples where numpy takes them; `out` must have the result's shape and must not share memory with x.
+
+_PAD_MODES = {'constant': 0, 'edge': 1, 'reflect': 2, 'symmetric': 3, 'wrap': 4}
+
+
+def _c_ints(values):
+    values = [int(v) for v in values]
+    return (B.c_int * builtins.max(len(values), 1))(*values)
+
+
+def _axes_tuple(axis) -> tuple:
+    return tuple(int(a) for a in axis) if isinstance(axis, (tuple, list)) else (int(axis),)
+
+
+def _along_axes(f, x: Tensor, axes, out) -> Tensor:
+    if axes is not None and len(_axes_tuple(axes)) == 0:                 # numpy: an empty tuple names no axis, the result is a copy
+        return roll(x, 0, axis=0, out=out)
+    axes = () if axes is None else _axes_tuple(axes)                    # n_axes == 0: every axis
+    return Tensor(f(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), len(axes), _c_ints(axes)), out is not None)
+
+
+def roll(x: Tensor, shift, axis=None, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.roll(x, shift, axis): shifts of any sign and size; axis=None rolls the flattened tensor and keeps the shape; shift and
+    axis broadcast against each other, and a repeated axis adds its shifts."""
+    shifts = _axes_tuple(shift)
+    if axis is None:
+        total = builtins.sum(shifts) % x.ne                              # Python's mod: in [0, ne)
+        return Tensor(B.dsc_roll(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), 0, _c_ints([total]), None), out is not None)
+    axes = _axes_tuple(axis)
+    if len(shifts) != len(axes):
+        if len(shifts) != 1 and len(axes) != 1:
+            raise ValueError(f'roll: shift {shift} and axis {axis} do not broadcast')
+        shifts, axes = shifts * (len(axes) if len(shifts) == 1 else 1), axes * (len(shifts) if len(axes) == 1 else 1)
+    if not axes:
+        raise ValueError('roll: no axis given')
+    # a shift beyond 32 bits is reduced here (the extent of a valid axis); an invalid axis goes through and ends in the library's message
+    shifts = [s % x.shape[a] if -x.n_dim <= a < x.n_dim and not -2 ** 31 <= s < 2 ** 31 else s for s, a in zip(shifts, axes)]
+    return Tensor(B.dsc_roll(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), len(axes), _c_ints(shifts), _c_ints(axes)), out is not None)
+
+
+def flip(x: Tensor, axis=None, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.flip(x, axis); axis=None flips every axis."""
+    return _along_axes(B.dsc_flip, x, axis, out)
+
+
+def fftshift(x: Tensor, axes=None, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.fft.fftshift(x, axes): the zero bin to the middle; axes=None shifts every axis."""
+    return _along_axes(B.dsc_fftshift, x, axes, out)
+
+
+def ifftshift(x: Tensor, axes=None, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.fft.ifftshift(x, axes): the inverse of fftshift (they differ on axes of odd length)."""
+    return _along_axes(B.dsc_ifftshift, x, axes, out)
+
+
+def pad(x: Tensor, pad_width, mode: str = 'constant', constant_values=0, out: Union[Tensor, None] = None) -> Tensor:
+    """numpy.pad(x, pad_width, mode) for mode 'constant', 'edge', 'reflect', 'symmetric' or 'wrap'; pad_width an int, a (before, after)
+    pair or one pair per axis, of any width; constant_values one scalar (complex for complex tensors)."""
+    if mode not in _PAD_MODES:
+        raise ValueError(f'pad: mode must be one of {sorted(_PAD_MODES)}, got {mode!r}')
+    widths = np.asarray(pad_width)
+    if widths.dtype.kind not in 'iu':
+        raise TypeError('pad: pad_width must be of integral type')
+    widths = np.broadcast_to(widths, (x.n_dim, 2))
+    value = complex(constant_values)
+    return Tensor(B.dsc_pad(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), _c_ints(widths.reshape(-1)), _PAD_MODES[mode], value.real, value.imag),
+                  out is not None)
+
+
 # ---- polyphase FIR resampling along the last axis (include/dsc_mi355x.h, Section H): scipy.signal.upfirdn / resample_poly / decimate
 # (ftype='fir') and the low-pass firwin, in one pass of the direct kernel; nothing is rounded to a power of two
 

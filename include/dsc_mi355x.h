@@ -423,6 +423,44 @@ dsc_tensor *dsc_unwrap(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int a
 dsc_tensor *dsc_phase (dsc_ctx *ctx, const dsc_tensor *z, dsc_tensor *out, int axis);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section J — index maps along axes (no reference counterpart).
+ *
+ * out[j0, j1, j2, j3] = x[m0(j0), m1(j1), m2(j2), m3(j3)] or a constant, each m a piecewise-affine map of one axis: one plan, one
+ * kernel family and ONE pass over memory, whatever the number of axes.  The four dtypes, 1 to 4 dims; elements move as opaque 4-, 8-
+ * and 16-byte words, so every result is bit-identical to numpy's (NaN payloads and -0 included).  Negative axes count from the end.
+ *   dsc_roll(x, shifts, axes)   numpy.roll(x, shifts, axes): n_axes shifts and axes; shifts of any sign and magnitude, reduced mod the
+ *                               extent in 64 bits; a repeated axis adds its shifts.  n_axes == 0: shifts[0] rolls the flattened tensor
+ *                               (numpy's axis=None), the result keeps x's shape.
+ *   dsc_flip(x, axes)           numpy.flip(x, axes); n_axes == 0: every axis.  A repeated axis is an argument error, as numpy raises.
+ *   dsc_fftshift(x, axes)       numpy.fft.fftshift(x, axes): a roll by n / 2 (rounded down) of every listed axis; n_axes == 0: every axis.
+ *   dsc_ifftshift(x, axes)      numpy.fft.ifftshift(x, axes): a roll by -(n / 2); its inverse, and different from it on an axis of odd n.
+ *   dsc_pad(x, pad_width, mode) numpy.pad(x, pad_width, mode).  pad_width [2 * x->n_dim]: (before, after) per axis of x in order, all >= 0,
+ *                               of any width, wider than the axis included (cropping is dsc_tensor_get_slice's).  mode 0 constant
+ *                               (value_re for real dtypes, value_re + i value_im for complex, rounded once to the dtype), 1 edge,
+ *                               2 reflect, 3 symmetric, 4 wrap.  With n the extent and t = j - before the source index is
+ *                                 wrap       t mod n                          edge       t clamped to [0, n - 1]
+ *                                 reflect    u = t mod 2 (n - 1); u if u < n, else 2 (n - 1) - u; 0 when n == 1
+ *                                 symmetric  u = t mod 2 n; u if u < n, else 2 n - 1 - u
+ *                               (mod with a result >= 0): numpy's iterated padding in closed form (tests/test_remap_abi.py).
+ * out: NULL or a tensor of the result's exact shape and x's dtype; it must not share memory with x (no in-place form).  Argument
+ * errors (an axis out of range, a repeated dsc_flip axis, a negative pad width, an unknown mode, a wrong out, an overlap, a padded
+ * result of more than 2^31 - 1 elements — the message names the shape) print and exit like every operator.
+ * dsc_last_fft_path, after neighbouring axes that are not mapped have been merged ([4096, 64, 256] rolled on axis 0 is 4096 rows):
+ *   "remap_rows"   the last axis is not mapped, its rows are whole 16-byte packs (at least 16 of them) and both tensors start on
+ *                  16-byte boundaries: a workgroup resolves the outer source indices once and copies aligned packs.
+ *   "remap_packs"  the last axis is mapped, 4- or 8-byte elements, OUTPUT rows of whole packs, aligned bases: every thread stores one
+ *                  aligned pack whose sources are consecutive words in either direction (one load of element alignment, swapped in
+ *                  registers when reversed) unless the pack straddles a seam of the map, where it gathers per element.
+ *   "remap_elems"  everything else (odd row bytes, unaligned bases, 16-byte elements with a mapped last axis, short rows): one element
+ *                  per thread.  DSC_REMAP_ROUTE=elems (read at every call) forces it on any shape.
+ */
+dsc_tensor *dsc_roll     (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n_axes, const int *shifts, const int *axes);
+dsc_tensor *dsc_flip     (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n_axes, const int *axes);
+dsc_tensor *dsc_fftshift (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n_axes, const int *axes);
+dsc_tensor *dsc_ifftshift(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n_axes, const int *axes);
+dsc_tensor *dsc_pad      (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, const int *pad_width, int mode, double value_re, double value_im);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
