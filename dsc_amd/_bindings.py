@@ -192,6 +192,12 @@ dsc_flip = _sig('dsc_flip', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c
 dsc_fftshift = _sig('dsc_fftshift', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, POINTER(c_int))
 dsc_ifftshift = _sig('dsc_ifftshift', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, POINTER(c_int))
 dsc_pad = _sig('dsc_pad', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, POINTER(c_int), c_int, c_double, c_double)
+dsc_sumsq = _sig('dsc_sumsq', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_bool)
+dsc_rms = _sig('dsc_rms', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_bool)
+dsc_var = _sig('dsc_var', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int, c_bool)
+dsc_std = _sig('dsc_std', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int, c_bool)
+dsc_vdot = _sig('dsc_vdot', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, _DscTensor_p, c_int, c_bool)
+dsc_detrend = _sig('dsc_detrend', _DscTensor_p, _DscCtx, _DscTensor_p, _DscTensor_p, c_int, c_int)
 
 
 class _DscIpcHandle(Structure):        # include/dsc_mi355x.h section C

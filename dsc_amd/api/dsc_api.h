@@ -2,7 +2,7 @@
 //
 // Mirror of the reference's dsc/api/dsc_api.h: `dsc::init`, RAII `dsc::tensor<T>`, the arithmetic operators, `dsc::pow`,
 // `dsc::cos .. sqrt`, `dsc::i0`, `dsc::clip`, `dsc::arange / randn`, `dsc::reshape / concat`, `dsc::sum`,
-// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope`, `dsc::upfirdn / resample_poly / decimate / firwin`, `dsc::cumsum / diff / unwrap / phase` and `dsc::roll / flip / fftshift / ifftshift / pad`.  The one semantic
+// `dsc::fft / ifft / rfft / irfft` (reference lines 15-21, 24-34, 36-143, 148-189, 260-319, 321-343) plus `dsc::filter_fft`, `dsc::stft / istft` `dsc::convolve / correlate`, `dsc::fft2 / ifft2 / rfft2 / irfft2` `dsc::hilbert / envelope`, `dsc::upfirdn / resample_poly / decimate / firwin`, `dsc::cumsum / diff / unwrap / phase`, `dsc::roll / flip / fftshift / ifftshift / pad` and `dsc::sumsq / rms / var / std / vdot / detrend`.  The one semantic
 // difference: tensor payloads live in HBM, so construction from host data and `to_host()`
 // copy through dsc_copy_from_host / dsc_copy_to_host instead of dereferencing `data()`
 // (reference: memcpy into x_->data, dsc_api.h:63-66).
@@ -324,6 +324,21 @@ static inline tensor<T> pad(const tensor<T> &x, std::initializer_list<int> pad_w
     w.resize(2 * (size_t) x.ndim(), 0);
     return dsc_pad(ctx, x.x_, nullptr, w.data(), mode, value_re, value_im);
 }
+
+// Section K of dsc_mi355x.h: moments along one axis, every sum in double.  sumsq / rms / var / std of a complex payload carry a real
+// one (as phase does); vdot(a, b) = sum conj(a) b; detrend takes out the mean (DSC_DETREND_CONSTANT) or the least-squares line
+template<typename T>
+static inline tensor<T> sumsq(const tensor<T> &x, int axis = -1, bool keep_dims = true) noexcept { return dsc_sumsq(ctx, x.x_, nullptr, axis, keep_dims); }
+template<typename T>
+static inline tensor<T> rms(const tensor<T> &x, int axis = -1, bool keep_dims = true) noexcept { return dsc_rms(ctx, x.x_, nullptr, axis, keep_dims); }
+template<typename T>
+static inline tensor<T> var(const tensor<T> &x, int axis = -1, int ddof = 0, bool keep_dims = true) noexcept { return dsc_var(ctx, x.x_, nullptr, axis, ddof, keep_dims); }
+template<typename T>
+static inline tensor<T> std(const tensor<T> &x, int axis = -1, int ddof = 0, bool keep_dims = true) noexcept { return dsc_std(ctx, x.x_, nullptr, axis, ddof, keep_dims); }
+template<typename T>
+static inline tensor<T> vdot(const tensor<T> &a, const tensor<T> &b, int axis = -1, bool keep_dims = true) noexcept { return dsc_vdot(ctx, a.x_, b.x_, nullptr, axis, keep_dims); }
+template<typename T>
+static inline tensor<T> detrend(const tensor<T> &x, int axis = -1, dsc_detrend_type type = DSC_DETREND_LINEAR) noexcept { return dsc_detrend(ctx, x.x_, nullptr, axis, type); }
 
 static inline void synchronize() noexcept { dsc_synchronize(ctx); }
 

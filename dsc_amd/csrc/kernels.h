@@ -288,6 +288,25 @@ void   dsc_launch_scan_cols(const void *x, void *out, int op, int dtype, long lo
 // out [outer][n - 1][inner] = x[.][j + 1][.] - x[.][j][.], n >= 2, fewer than 2^31 output elements
 void   dsc_launch_scan_diff(const void *x, void *out, int dtype, long long outer, int n, long long inner, hipStream_t stream);
 
+// ---- centred moments along one axis (dsc_sumsq / dsc_rms / dsc_var / dsc_std / dsc_vdot / dsc_detrend, moments.cpp) ------
+// x (and y, vdot only: the same shape and dtype, else NULL) viewed as [outer][n][inner] contiguous (moments.hip).  op: 0 sumsq / rms
+// (root), 1 vdot = sum conj(x) y, 2 var / std (root), 3 detrend constant, 4 detrend linear; dtype is x's, every sum a double.  out: one
+// element per (outer, inner) of x's real dtype (op 0, 2) or of x's dtype (op 1); detrend: x's shape and dtype, not overlapping x.
+// rows / tiles: inner == 1, x = [rows][n].  rows: one launch, a wave or workgroup per row.  tiles: two to four launches (tile sums, the
+// statistic per row, the centred pass per tile, its sums per row) and dsc_moment_scratch_bytes(rows, tiles per row) bytes of scratch,
+// 256-byte aligned; a tile is dsc_moment_tile_len() elements, which is also the longest row that stays in registers between the two
+// passes of the rows route.  cols: any inner; n_seg from dsc_moment_cols_segments() (1: one thread walks the whole axis, no scratch),
+// which never asks for more than scratch_bytes = dsc_moment_scratch_bytes(outer inner, n_seg).
+int    dsc_moment_tile_len(int dtype);
+size_t dsc_moment_scratch_bytes(long long n_out, long long n_seg);
+void   dsc_launch_moment_rows(const void *x, const void *y, void *out, int op, int dtype, long long rows, int n, int ddof, bool root,
+                              hipStream_t stream);
+void   dsc_launch_moment_tiles(const void *x, const void *y, void *out, int op, int dtype, long long rows, int n, int ddof, bool root,
+                               void *scratch, hipStream_t stream);
+int    dsc_moment_cols_segments(long long n_out, int n, size_t scratch_bytes);
+void   dsc_launch_moment_cols(const void *x, const void *y, void *out, int op, int dtype, long long outer, int n, long long inner, int ddof,
+                              bool root, int n_seg, void *scratch, hipStream_t stream);
+
 // ---- strided gather / scatter of a slice region (indexing.cpp) -----------------------------
 // Region of a tensor: element (i0, i1, i2, i3), i_d < count[d], sits at base + sum_d i_d * stride[d]
 // (elements; strides may be negative).  Row-major order over the region = flat index of the dense side.

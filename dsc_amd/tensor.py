@@ -462,6 +462,42 @@ def phase(z: Tensor, axis: int = -1, out: Union[Tensor, None] = None) -> Tensor:
     return _scan(B.dsc_phase, z, axis, out)
 
 
+# ---- moments along one axis (include/dsc_mi355x.h, Section K): every sum in double, var centred on the computed mean (two passes)
+def sumsq(x: Tensor, out=None, axis: int = -1, keepdims: bool = True) -> Tensor:
+    """sum |x|^2 along the axis in one read; real for complex x."""
+    return _reduce(B.dsc_sumsq, x, out, axis, keepdims)
+
+
+def rms(x: Tensor, out=None, axis: int = -1, keepdims: bool = True) -> Tensor:
+    """sqrt(sumsq(x) / n)."""
+    return _reduce(B.dsc_rms, x, out, axis, keepdims)
+
+
+def var(x: Tensor, out=None, axis: int = -1, ddof: int = 0, keepdims: bool = True) -> Tensor:
+    """numpy.var(x, axis, ddof=ddof); real for complex x."""
+    return Tensor(B.dsc_var(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), int(axis), int(ddof), keepdims), out is not None)
+
+
+def std(x: Tensor, out=None, axis: int = -1, ddof: int = 0, keepdims: bool = True) -> Tensor:
+    """numpy.std(x, axis, ddof=ddof)."""
+    return Tensor(B.dsc_std(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), int(axis), int(ddof), keepdims), out is not None)
+
+
+def vdot(a: Tensor, b: Tensor, out=None, axis: int = -1, keepdims: bool = True) -> Tensor:
+    """sum conj(a) b along the axis; a and b of one shape and dtype (no broadcasting)."""
+    return Tensor(B.dsc_vdot(_get_ctx(), a._c_ptr, b._c_ptr, _c_ptr_or_none(out), int(axis), keepdims), out is not None)
+
+
+_DETREND_TYPES = {'constant': 0, 'linear': 1}
+
+
+def detrend(x: Tensor, axis: int = -1, type: str = 'linear', out: Union[Tensor, None] = None) -> Tensor:
+    """scipy.signal.detrend(x, axis, type): the mean ('constant') or the least-squares line ('linear') taken out along the axis."""
+    if type not in _DETREND_TYPES:
+        raise ValueError(f"type must be 'linear' or 'constant', got {type!r}")
+    return Tensor(B.dsc_detrend(_get_ctx(), x._c_ptr, _c_ptr_or_none(out), int(axis), _DETREND_TYPES[type]), out is not None)
+
+
 # ---- index maps along axes (include/dsc_mi355x.h, Section J): numpy.roll / flip / fft.fftshift / fft.ifftshift / pad in one pass, bit-identical
 # to numpy.  Ints or tuples where numpy takes them; `out` must have the result's shape and must not share memory with x.
 

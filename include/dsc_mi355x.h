@@ -461,6 +461,46 @@ dsc_tensor *dsc_ifftshift(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, in
 dsc_tensor *dsc_pad      (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, const int *pad_width, int mode, double value_re, double value_im);
 
 /* ---------------------------------------------------------------------------------------------
+ * Section K — moments along one axis (no reference counterpart).
+ *
+ * Along `axis` of x (any axis, negative counts from the end; at most 4 dims), the tensor viewed as [outer][n][inner] like the
+ * reductions; f32 / f64 / c32 / c64.  Every sum is accumulated in double, for f32 / c32 data too (the product of two floats is exact
+ * there), and every result is rounded once to its dtype.  With m = (sum x[j]) / n:
+ *   dsc_sumsq(x)          sum |x[j]|^2: one read of x, no complex intermediate.  A complex x gives its real dtype, as dsc_abs does.
+ *   dsc_rms(x)            sqrt(sumsq / n).
+ *   dsc_var(x, ddof)      numpy.var(x, axis, ddof) = sum |x[j] - m|^2 / (n - ddof), centred on the computed mean: the two-pass
+ *                         definition, which keeps its digits on data with an offset (neither sum |x|^2 - n |m|^2 nor merged
+ *                         (count, mean, M2) triples do).  Real dtype of x.  ddof < 0 or ddof >= n is an argument error.
+ *   dsc_std(x, ddof)      sqrt of it.
+ *   dsc_vdot(a, b)        sum conj(a[j]) b[j]: a and b of one shape and dtype (no broadcasting), the result of that dtype.
+ *   dsc_detrend(x, type)  scipy.signal.detrend(x, axis, type): with t[j] = j - (n - 1) / 2 and b = sum t[j] x[j] / (n (n^2 - 1) / 12),
+ *                         out[j] = x[j] - m - b t[j] (DSC_DETREND_LINEAR, the least-squares line; n == 1 subtracts the mean only) or
+ *                         out[j] = x[j] - m (DSC_DETREND_CONSTANT), per component of complex data.  x's shape and dtype.
+ * keep_dims and the shape of a reduction's result are dsc_sum's.  out: NULL or a tensor of the result's shape and dtype; it must not
+ * share memory with an input.  No floating-point atomics: partial sums are combined in index order, two identical calls give
+ * identical bits.  Argument errors (a wrong out, an overlap, an axis out of range, a bad ddof, operands of dsc_vdot that differ in
+ * shape or dtype, an unknown type) print and exit like every operator.
+ * dsc_last_fft_path (detrend_rows / detrend_tiles / detrend_cols for dsc_detrend):
+ *   "moment_rows"   inner == 1, 1024 rows or more (or rows of at most one tile): a workgroup per row — a wave per row for 1024
+ *                   rows or more of at most a quarter of a tile — in 16-byte packs.  A row of at most one tile (32 KiB: 8192 f32, 4096 f64 / c32,
+ *                   2048 c64; a quarter of that per wave; 2048 / 512 elements where the length or the address rules packs out) stays in
+ *                   registers between the mean and the centred pass of var and detrend: one HBM read, plus one write for detrend.  A
+ *                   longer row is read a second time by the same workgroup.
+ *   "moment_tiles"  inner == 1, fewer than 1024 rows longer than a tile: per-tile sums to scratch, the statistic per row, the centred
+ *                   pass per tile, its sums per row in tile order: two (sumsq, vdot), three (detrend) or four (var) plain launches.
+ *   "moment_cols"   inner > 1: one thread per (outer, inner) element walks the axis, neighbouring threads on neighbouring addresses;
+ *                   with fewer than 65536 outputs and an axis of at least 128 the axis is cut into segments combined in order.
+ * DSC_MOMENT_ROUTE=rows|tiles (read at every call) forces either route on any inner == 1 shape.
+ */
+typedef enum { DSC_DETREND_CONSTANT = 0, DSC_DETREND_LINEAR = 1 } dsc_detrend_type;
+dsc_tensor *dsc_sumsq  (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis, bool keep_dims);
+dsc_tensor *dsc_rms    (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis, bool keep_dims);
+dsc_tensor *dsc_var    (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis, int ddof, bool keep_dims);
+dsc_tensor *dsc_std    (dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis, int ddof, bool keep_dims);
+dsc_tensor *dsc_vdot   (dsc_ctx *ctx, const dsc_tensor *a, const dsc_tensor *b, dsc_tensor *out, int axis, bool keep_dims);
+dsc_tensor *dsc_detrend(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis, dsc_detrend_type type);
+
+/* ---------------------------------------------------------------------------------------------
  * Section C — multi-GPU reassembly of batch-sharded outputs.
  *
  * No reference counterpart: the reference has one backend (CPU, dsc/include/dsc_backend.h:11-13) and no communication
