@@ -1,9 +1,9 @@
 // dsc_capi.cpp — context, HBM arenas, tensors, copies, creation (arange / randn), reshape / concat, cast, binary and
-// unary operators, reductions of the C ABI declared in include/dsc_mi355x.h.  FFT entry points live in fft_driver.cpp.
+// unary operators of the C ABI declared in include/dsc_mi355x.h.  FFT entry points live in fft_driver.cpp, reductions in reduce.cpp.
 //
 // Host-side mirror of dsc/src/dsc.cpp:136-470 (context + tensor creation), :44-115
 // (parameter validation), :481-534 (arange / randn), :600-720 (reshape / concat), :1273-1297 (binary operators),
-// :1299-1440 and :1640-1770 (unary operators, i0, clip) and :1793-1953 (reductions); arithmetic is in
+// :1299-1440 and :1640-1770 (unary operators, i0, clip); arithmetic is in
 // the .hip files.  Error behaviour is the reference's: print and exit (dsc.h:14-28).
 #include "dsc_internal.h"
 #include "kernels.h"
@@ -612,53 +612,3 @@ extern "C" dsc_tensor *dsc_concat(dsc_ctx *ctx, int axis, int tensors, ...) {
     }
     return out;
 }
-
-// ------------------------------------------------------------------------------ reductions
-
-// dsc.cpp:83-115 (validate_reduce_params).  For keep_dims=false the reference leaves
-// 0x01010101 in the leading slots of its scratch shape (memset with 1, :98), which only a
-// user-supplied `out` can observe; here those slots are 1 and such an `out` is accepted.
-static dsc_tensor *reduce_entry(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis, bool keep_dims, int op) {
-    DSC_ASSERT(x != nullptr);
-    static const char *names[] = {"dsc_sum", "dsc_mean", "dsc_max", "dsc_min"};
-    dsc_trace_scope trace__(ctx, names[op], "op;unary", x, nullptr, 0, axis);
-    const int slot = dsc_axis_slot(x, axis);
-    DSC_ASSERT(slot >= 0 && slot < DSC_MAX_DIMS);
-
-    int out_shape[DSC_MAX_DIMS];
-    int out_ndim = x->n_dim;
-    if (keep_dims) {
-        memcpy(out_shape, x->shape, sizeof(out_shape));
-        out_shape[slot] = 1;
-    } else {
-        out_ndim--;
-        const int lead = DSC_MAX_DIMS - out_ndim;
-        for (int i = 0; i < lead; ++i) out_shape[i] = 1;
-        for (int xi = DSC_MAX_DIMS - x->n_dim, oi = 0; xi < DSC_MAX_DIMS; ++xi) {
-            if (xi == slot) continue;
-            out_shape[lead + oi++] = x->shape[xi];
-        }
-    }
-    if (out == nullptr) {
-        out = dsc_new_tensor(ctx, out_ndim, &out_shape[DSC_MAX_DIMS - out_ndim], x->dtype, nullptr);
-    } else {
-        DSC_ASSERT(out->dtype == x->dtype);
-        DSC_ASSERT(out->n_dim == out_ndim);
-        DSC_ASSERT(memcmp(out->shape, out_shape, sizeof(out_shape)) == 0);
-    }
-
-    long long outer = 1, inner = 1;
-    for (int i = 0; i < slot; ++i) outer *= x->shape[i];
-    for (int i = slot + 1; i < DSC_MAX_DIMS; ++i) inner *= x->shape[i];
-    // workspace for the segmented path: whatever the scratch arena has, up to 64 MiB
-    ctx->scratch.reset();
-    size_t ws_bytes = ctx->scratch.capacity() > (64u << 20) ? (64u << 20) : ctx->scratch.capacity() / 2;
-    void *ws = ws_bytes >= 4096 ? ctx->scratch.alloc(ws_bytes) : nullptr;
-    dsc_launch_reduce(x->data, out->data, x->dtype, op, outer, x->shape[slot], inner, ws, ws_bytes, ctx->stream);
-    return out;
-}
-
-extern "C" dsc_tensor *dsc_sum (dsc_ctx *c, const dsc_tensor *x, dsc_tensor *o, int axis, bool keep) { return reduce_entry(c, x, o, axis, keep, 0); }
-extern "C" dsc_tensor *dsc_mean(dsc_ctx *c, const dsc_tensor *x, dsc_tensor *o, int axis, bool keep) { return reduce_entry(c, x, o, axis, keep, 1); }
-extern "C" dsc_tensor *dsc_max (dsc_ctx *c, const dsc_tensor *x, dsc_tensor *o, int axis, bool keep) { return reduce_entry(c, x, o, axis, keep, 2); }
-extern "C" dsc_tensor *dsc_min (dsc_ctx *c, const dsc_tensor *x, dsc_tensor *o, int axis, bool keep) { return reduce_entry(c, x, o, axis, keep, 3); }

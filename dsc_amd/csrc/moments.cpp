@@ -26,43 +26,11 @@ constexpr long long kTilesBelowRows = 1024;
 
 enum { K_SUMSQ = 0, K_VDOT = 1, K_VAR = 2, K_DETREND_C = 3, K_DETREND_L = 4 };      // the codes of moments.hip
 
-struct axis_view { int slot, n; long long outer, inner; };
-
-axis_view view_of(const dsc_tensor *x, int axis) {
-    if (x->n_dim < 1 || x->n_dim > DSC_MAX_DIMS) DSC_LOG_FATAL("tensors have 1 to %d dimensions, got %d", DSC_MAX_DIMS, x->n_dim);
-    if (axis < -x->n_dim || axis >= x->n_dim) DSC_LOG_FATAL("axis %d is out of range for a tensor of %d dimensions", axis, x->n_dim);
-    axis_view v;
-    v.slot = dsc_axis_slot(x, axis);
-    v.n = x->shape[v.slot];
-    v.outer = v.inner = 1;
-    for (int i = 0; i < v.slot; ++i) v.outer *= x->shape[i];
-    for (int i = v.slot + 1; i < DSC_MAX_DIMS; ++i) v.inner *= x->shape[i];
-    return v;
-}
-
-// the shape of a reduction's result, as reduce_entry (dsc_capi.cpp) forms it: the axis kept with extent 1, or dropped
-int reduced_shape(const dsc_tensor *x, int slot, bool keep_dims, int (&out_shape)[DSC_MAX_DIMS]) {
-    int out_ndim = x->n_dim;
-    if (keep_dims) {
-        memcpy(out_shape, x->shape, sizeof(out_shape));
-        out_shape[slot] = 1;
-        return out_ndim;
-    }
-    out_ndim--;
-    const int lead = DSC_MAX_DIMS - out_ndim;
-    for (int i = 0; i < lead; ++i) out_shape[i] = 1;
-    for (int xi = DSC_MAX_DIMS - x->n_dim, oi = 0; xi < DSC_MAX_DIMS; ++xi) {
-        if (xi == slot) continue;
-        out_shape[lead + oi++] = x->shape[xi];
-    }
-    return out_ndim;
-}
-
 // op: a code of moments.hip; y: the second operand of vdot; root: rms / std
 dsc_tensor *moment_impl(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *y, dsc_tensor *out, int axis, bool keep_dims, int op,
                         int ddof, bool root) {
     DSC_ASSERT(x != nullptr);
-    const axis_view v = view_of(x, axis);
+    const dsc_axis_view v = dsc_axis_view_of(x, axis);
     const bool detrend = op >= K_DETREND_C;
     if (op == K_VDOT) {
         DSC_ASSERT(y != nullptr);
@@ -76,7 +44,7 @@ dsc_tensor *moment_impl(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *y, 
     } else {
         const dsc_dtype odt = op == K_VDOT ? x->dtype : x->dtype == DSC_C32 ? DSC_F32 : x->dtype == DSC_C64 ? DSC_F64 : x->dtype;
         int out_shape[DSC_MAX_DIMS];
-        const int out_ndim = reduced_shape(x, v.slot, keep_dims, out_shape);
+        const int out_ndim = dsc_reduced_shape(x->shape, x->n_dim, v.slot, keep_dims, out_shape);
         DSC_RESULT(out, ctx, out_ndim, out_shape, odt, "the reduced shape (%s the axis) and the result's dtype", keep_dims ? "1 along" : "without");
     }
     DSC_NO_OVERLAP(out, x, "the input");
@@ -85,30 +53,21 @@ dsc_tensor *moment_impl(dsc_ctx *ctx, const dsc_tensor *x, const dsc_tensor *y, 
     const char *const routes[2][3] = {{"moment_rows", "moment_tiles", "moment_cols"}, {"detrend_rows", "detrend_tiles", "detrend_cols"}};
     const void *yd = y != nullptr ? y->data : nullptr;
     if (v.inner > 1) {
-        ctx->scratch.reset();
         const size_t cap = ctx->scratch.capacity() > DSC_DEVICE_ALIGN ? ctx->scratch.capacity() - DSC_DEVICE_ALIGN : 0;
-        const int n_seg = dsc_moment_cols_segments(v.outer * v.inner, v.n, cap);
-        char *scratch = n_seg > 1 ? ctx->scratch.alloc(dsc_moment_scratch_bytes(v.outer * v.inner, n_seg)) : nullptr;
-        dsc_launch_moment_cols(x->data, yd, out->data, op, x->dtype, v.outer, v.n, v.inner, ddof, root, n_seg, scratch, ctx->stream);
-        ctx->scratch.reset();                                            // the stream is in order: nothing reuses the block before the launches have read it
+        const long long n_out = v.outer * v.inner;
+        const int n_seg = dsc_moment_cols_segments(n_out, v.n, cap);
+        const size_t need = n_seg > 1 ? dsc_moment_scratch_bytes(n_out, n_seg) : 0;
+        DSC_SCRATCH_BLOCK(scratch, ctx, need, "the segment sums of %lld columns need %.2f MB", n_out, (double) need / 1048576.);
+        dsc_launch_moment_cols(x->data, yd, out->data, op, x->dtype, v.outer, v.n, v.inner, ddof, root, n_seg, scratch.ptr, ctx->stream);
         ctx->last_fft_path = routes[detrend][2];
         return out;
     }
     const int tile_len = dsc_moment_tile_len(x->dtype);
-    bool tiles = v.outer < kTilesBelowRows && v.n > tile_len;
-    if (const char *forced = getenv("DSC_MOMENT_ROUTE")) {               // read at every call: the tests and tools/bench_moments.py switch it
-        if (strcmp(forced, "rows") == 0) tiles = false;
-        else if (strcmp(forced, "tiles") == 0) tiles = true;
-        else DSC_LOG_FATAL("DSC_MOMENT_ROUTE must be rows or tiles, got \"%s\"", forced);
-    }
-    if (tiles) {
+    const int forced = dsc_forced_route("DSC_MOMENT_ROUTE", {"rows", "tiles"});
+    if (forced >= 0 ? forced == 1 : v.outer < kTilesBelowRows && v.n > tile_len) {
         const size_t need = dsc_moment_scratch_bytes(v.outer, (v.n + tile_len - 1) / tile_len);
-        ctx->scratch.reset();
-        if (ctx->scratch.capacity() < need + DSC_DEVICE_ALIGN)
-            DSC_LOG_FATAL("scratch arena too small: the tile sums of %lld rows of %d need %.2f MB", v.outer, v.n, (double) need / 1048576.);
-        char *scratch = ctx->scratch.alloc(need);
-        dsc_launch_moment_tiles(x->data, yd, out->data, op, x->dtype, v.outer, v.n, ddof, root, scratch, ctx->stream);
-        ctx->scratch.reset();
+        DSC_SCRATCH_BLOCK(scratch, ctx, need, "the tile sums of %lld rows of %d need %.2f MB", v.outer, v.n, (double) need / 1048576.);
+        dsc_launch_moment_tiles(x->data, yd, out->data, op, x->dtype, v.outer, v.n, ddof, root, scratch.ptr, ctx->stream);
         ctx->last_fft_path = routes[detrend][1];
     } else {
         dsc_launch_moment_rows(x->data, yd, out->data, op, x->dtype, v.outer, v.n, ddof, root, ctx->stream);

@@ -417,8 +417,6 @@ template<typename F> void with_moment_types(int op, int dtype, F f) {
     with_index<5>("moments.hip", "operator", op, [&](auto opc) { with_dtype(dtype, [&](auto in) { f(opc, in); }); });
 }
 
-size_t block_bytes(long long n, size_t elem) { return ((size_t) n * elem + 255) & ~(size_t) 255; }
-
 }  // namespace
 
 int dsc_moment_tile_len(int dtype) {
@@ -428,7 +426,7 @@ int dsc_moment_tile_len(int dtype) {
 }
 
 size_t dsc_moment_scratch_bytes(long long n_out, long long n_seg) {
-    return block_bytes(n_out * n_seg, kAcc * sizeof(double)) + block_bytes(n_out, kAcc * sizeof(double));
+    return scratch_block_bytes(n_out * n_seg, kAcc * sizeof(double)) + scratch_block_bytes(n_out, kAcc * sizeof(double));
 }
 
 void dsc_launch_moment_rows(const void *x, const void *y, void *out, int op, int dtype, long long rows, int n, int ddof, bool root,
@@ -454,7 +452,7 @@ void dsc_launch_moment_tiles(const void *x, const void *y, void *out, int op, in
         constexpr int tile_len = tile_len_of<In>();
         const int tiles_per_row = (n + tile_len - 1) / tile_len;
         const long long n_seg = rows * tiles_per_row;
-        double *partial = (double *) scratch, *stats = (double *) ((char *) scratch + block_bytes(n_seg, kAcc * sizeof(double)));
+        double *partial = (double *) scratch, *stats = (double *) ((char *) scratch + scratch_block_bytes(n_seg, kAcc * sizeof(double)));
         const In *xp = (const In *) x, *yp = (const In *) y;
         launch_seg<OP, In, kThreads, PART0>(xp, yp, out, partial, nullptr, n_seg, n, tile_len, tiles_per_row, ddof, root, stream);
         launch_combine<OP, In, 0>(partial, stats, out, rows, tiles_per_row, n, ddof, root, stream);
@@ -490,7 +488,7 @@ void dsc_launch_moment_cols(const void *x, const void *y, void *out, int op, int
             return;
         }
         const int seg_len = (n + n_seg - 1) / n_seg;
-        double *partial = (double *) scratch, *stats = (double *) ((char *) scratch + block_bytes(n_out * n_seg, kAcc * sizeof(double)));
+        double *partial = (double *) scratch, *stats = (double *) ((char *) scratch + scratch_block_bytes(n_out * n_seg, kAcc * sizeof(double)));
         const dim3 grid((unsigned) ((n_out + kThreads - 1) / kThreads), (unsigned) n_seg);
         DSC_LAUNCH((moment_cols_seg_kernel<OP, In, 0>), grid, dim3(kThreads), 0, stream, xp, yp, out, partial, (const double *) nullptr,
                    outer, n, inner, seg_len, n_seg);

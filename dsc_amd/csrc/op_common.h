@@ -1,4 +1,4 @@
-// op_common.h — what the operator files (stft, conv, hilbert, fft2, resample, scan .cpp) share on the host side: DESIGN.md 4.0b.
+// op_common.h — what the operator files (stft, conv, hilbert, fft2, resample, reduce, scan, moments, remap .cpp) share on the host side: DESIGN.md 4.0b.
 // One rule per helper.  The first part is arithmetic on integers and needs nothing but <cstddef>: define DSC_OP_COMMON_PURE before
 // including it from a stand-alone host program (tests/test_op_common.py).
 #pragma once
@@ -32,10 +32,52 @@ static inline long long dsc_fused_rows_per_launch(long long limit_bytes, long lo
     return rows_per;
 }
 
+// ---- the axis operators (reduce, scan, moments, remap .cpp): a tensor viewed as [outer][n][inner] around one of its four shape slots
+enum { DSC_OP_DIMS = 4 };                        // DSC_MAX_DIMS, which the pure part does not see
+struct dsc_axis_view { int slot, n; long long outer, inner; };
+
+// The view around a slot, unchecked: the reductions take a slot among the leading padding slots too, an extent of 1.
+static inline dsc_axis_view dsc_axis_view_at(const int *shape, int slot) {
+    dsc_axis_view v = {slot, shape[slot], 1, 1};
+    for (int i = 0; i < slot; ++i) v.outer *= shape[i];
+    for (int i = slot + 1; i < DSC_OP_DIMS; ++i) v.inner *= shape[i];
+    return v;
+}
+
+// The view along the user's axis of a shape right-aligned in the four slots; slot -1 when n_dim is outside 1..4 or axis is outside
+// [-n_dim, n_dim).  The slot is dsc_axis_slot's.
+static inline dsc_axis_view dsc_axis_view_on(const int *shape, int n_dim, int axis) {
+    if (n_dim < 1 || n_dim > DSC_OP_DIMS || axis < -n_dim || axis >= n_dim) return dsc_axis_view{-1, 0, 0, 0};
+    return dsc_axis_view_at(shape, axis < 0 ? DSC_OP_DIMS + axis : DSC_OP_DIMS - n_dim + axis);
+}
+
+// The shape of a reduction's result, the reference's rule (validate_reduce_params): the axis kept with extent 1, or dropped with ones
+// in the leading slots (filled from the right: the padding slots of `shape` hold 1).  Returns the result's rank.
+static inline int dsc_reduced_shape(const int *shape, int n_dim, int slot, bool keep_dims, int *out_shape) {
+    int oi = DSC_OP_DIMS - 1;
+    for (int xi = DSC_OP_DIMS - 1; xi >= 0; --xi)
+        if (keep_dims || xi != slot) out_shape[oi--] = xi == slot ? 1 : shape[xi];
+    while (oi >= 0) out_shape[oi--] = 1;
+    return keep_dims ? n_dim : n_dim - 1;
+}
+
+// The index of `value` among n_names route names, or -1.
+static inline int dsc_route_index(const char *value, const char *const *names, int n_names) {
+    for (int i = 0; i < n_names; ++i) {
+        const char *a = value, *b = names[i];
+        while (*a != '\0' && *a == *b) ++a, ++b;
+        if (*a == '\0' && *b == '\0') return i;
+    }
+    return -1;
+}
+
 #ifndef DSC_OP_COMMON_PURE
 #include "dsc_internal.h"
 
 #include <cstring>
+#include <initializer_list>
+
+static_assert(DSC_OP_DIMS == DSC_MAX_DIMS, "op_common.h counts the shape slots of dsc_tensor");
 
 // The result: a new tensor of the expected rank, shape (all DSC_MAX_DIMS slots) and dtype, or the caller's `out` if it is one.  A wrong
 // `out` ends the process with "out must have <what>", what being the caller's printf format and arguments.
@@ -86,6 +128,52 @@ struct __attribute__((visibility("hidden"))) dsc_scratch_pin {
     void pin() { arena.pin(); }
 };
 
+// A scratch block for an operator's own launches, nothing else using the arena meanwhile: reset() on entry, `need` bytes if the arena
+// has them with their alignment slack (need == 0: no block), reset() on every way out — the stream is in order, nothing reuses the block
+// before the launches have read it.  DSC_SCRATCH_BLOCK declares one; a short arena ends the process with "scratch arena too small: <what>".
+struct __attribute__((visibility("hidden"))) dsc_scratch_block {
+    dsc_scratch_arena &arena;
+    char *ptr = nullptr;
+    bool fits;
+    dsc_scratch_block(dsc_ctx *ctx, size_t need) : arena(ctx->scratch) {
+        arena.reset();
+        fits = need == 0 || arena.capacity() >= need + DSC_DEVICE_ALIGN;
+        if (fits && need > 0) ptr = arena.alloc(need);
+    }
+    ~dsc_scratch_block() { arena.reset(); }
+    dsc_scratch_block(const dsc_scratch_block &) = delete;
+};
+#define DSC_SCRATCH_BLOCK(name, ctx, need, ...) \
+    dsc_scratch_block name((ctx), (need));      \
+    if (!name.fits) DSC_LOG_FATAL("scratch arena too small: " __VA_ARGS__)
+
 // The DSC_NO_..._FUSED switches are read at every call: the tests and tools/bench_*.py switch routes within one process.
 static inline bool dsc_env_set(const char *name) { return getenv(name) != nullptr; }
+
+// A route forced by the environment variable `var`, read at every call like the switches above: the index of its value among the
+// allowed names, -1 when it is not set.  Any other value ends the process with "<var> must be a or b, got "x"".
+static inline int dsc_forced_route(const char *var, std::initializer_list<const char *> names) {
+    const char *value = getenv(var);
+    if (value == nullptr) return -1;
+    const int route = dsc_route_index(value, names.begin(), (int) names.size());
+    if (route < 0) {
+        char allowed[96] = "";
+        for (const char *name : names) snprintf(allowed + strlen(allowed), sizeof(allowed) - strlen(allowed), allowed[0] ? " or %s" : "%s", name);
+        DSC_LOG_FATAL("%s must be %s, got \"%s\"", var, allowed, value);
+    }
+    return route;
+}
+
+// x's view along the user's axis, and that axis's slot alone (remap.cpp, which maps several axes in one call); a rank outside
+// 1..DSC_MAX_DIMS and an axis outside [-n_dim, n_dim) end the process.
+static inline void dsc_check_rank(const dsc_tensor *x) {
+    if (x->n_dim < 1 || x->n_dim > DSC_MAX_DIMS) DSC_LOG_FATAL("tensors have 1 to %d dimensions, got %d", DSC_MAX_DIMS, x->n_dim);
+}
+static inline dsc_axis_view dsc_axis_view_of(const dsc_tensor *x, int axis) {
+    dsc_check_rank(x);
+    const dsc_axis_view v = dsc_axis_view_on(x->shape, x->n_dim, axis);
+    if (v.slot < 0) DSC_LOG_FATAL("axis %d is out of range for a tensor of %d dimensions", axis, x->n_dim);
+    return v;
+}
+static inline int dsc_checked_axis_slot(const dsc_tensor *x, int axis) { return dsc_axis_view_of(x, axis).slot; }
 #endif

@@ -19,15 +19,10 @@ namespace {
 
 const char *const kRouteNames[] = {"remap_rows", "remap_packs", "remap_elems"};
 
-int slot_of(const dsc_tensor *x, int axis) {
-    if (axis < -x->n_dim || axis >= x->n_dim) DSC_LOG_FATAL("axis %d is out of range for a tensor of %d dimensions", axis, x->n_dim);
-    return dsc_axis_slot(x, axis);
-}
-
 // the identity on every axis of x
 dsc_remap plan_of(const dsc_tensor *x) {
     DSC_ASSERT(x != nullptr);
-    if (x->n_dim < 1 || x->n_dim > DSC_MAX_DIMS) DSC_LOG_FATAL("tensors have 1 to %d dimensions, got %d", DSC_MAX_DIMS, x->n_dim);
+    dsc_check_rank(x);
     dsc_remap p{};
     for (int i = 0; i < DSC_MAX_DIMS; ++i) p.ax[i] = dsc_map_identity(x->shape[i]);
     return p;
@@ -44,10 +39,7 @@ dsc_tensor *run(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, dsc_remap &p
     DSC_ASSERT(p.ne_out == out->ne);
     const int elem_bytes = (int) dsc_dtype_size(x->dtype);
     int route = dsc_remap_route(p, elem_bytes, (((size_t) x->data | (size_t) out->data) & 15) == 0);
-    if (const char *forced = getenv("DSC_REMAP_ROUTE")) {                // read at every call: the tests and tools/bench_remap.py switch it
-        if (strcmp(forced, "elems") == 0) route = DSC_REMAP_ELEMS;
-        else DSC_LOG_FATAL("DSC_REMAP_ROUTE must be elems, got \"%s\"", forced);
-    }
+    if (dsc_forced_route("DSC_REMAP_ROUTE", {"elems"}) == 0) route = DSC_REMAP_ELEMS;
     dsc_launch_remap(x->data, out->data, elem_bytes, p, route, ctx->stream);
     ctx->last_fft_path = kRouteNames[route];
     return out;
@@ -62,7 +54,7 @@ dsc_tensor *shift_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int n
         for (int i = DSC_MAX_DIMS - x->n_dim; i < DSC_MAX_DIMS; ++i) shift[i] = sign * (long long) (x->shape[i] / 2);
     } else {
         for (int k = 0; k < n_axes; ++k) {
-            const int slot = slot_of(x, axes[k]);
+            const int slot = dsc_checked_axis_slot(x, axes[k]);
             shift[slot] += sign * (long long) (x->shape[slot] / 2);
         }
     }
@@ -82,7 +74,7 @@ extern "C" dsc_tensor *dsc_roll(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *o
         return run(ctx, x, out, p, true);
     }
     long long shift[DSC_MAX_DIMS] = {0, 0, 0, 0};
-    for (int k = 0; k < n_axes; ++k) shift[slot_of(x, axes[k])] += shifts[k];      // a repeated axis adds its shifts, as numpy does
+    for (int k = 0; k < n_axes; ++k) shift[dsc_checked_axis_slot(x, axes[k])] += shifts[k];      // a repeated axis adds its shifts, as numpy does
     for (int i = 0; i < DSC_MAX_DIMS; ++i) p.ax[i] = dsc_map_roll(x->shape[i], shift[i]);
     return run(ctx, x, out, p);
 }
@@ -93,7 +85,7 @@ extern "C" dsc_tensor *dsc_flip(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *o
     if (n_axes < 0 || (n_axes > 0 && axes == nullptr)) DSC_LOG_FATAL("n_axes must be >= 0 with that many axes, got %d", n_axes);
     bool seen[DSC_MAX_DIMS] = {false, false, false, false};
     for (int k = 0; k < n_axes; ++k) {
-        const int slot = slot_of(x, axes[k]);
+        const int slot = dsc_checked_axis_slot(x, axes[k]);
         if (seen[slot]) DSC_LOG_FATAL("repeated axis %d", axes[k]);
         seen[slot] = true;
     }

@@ -25,22 +25,8 @@ namespace {
 // DESIGN 4.10): scan_tiles / scan_rows = 0.63 (cumsum f32) and 0.53 (unwrap f32) at 64 rows, 1.07 and 1.01 at 128, 1.46 and 1.50 at 192.
 constexpr long long kTilesBelowRows = 128;
 
-struct axis_view { int slot, n; long long outer, inner; };
-
-axis_view view_of(const dsc_tensor *x, int axis) {
-    if (x->n_dim < 1 || x->n_dim > DSC_MAX_DIMS) DSC_LOG_FATAL("tensors have 1 to %d dimensions, got %d", DSC_MAX_DIMS, x->n_dim);
-    if (axis < -x->n_dim || axis >= x->n_dim) DSC_LOG_FATAL("axis %d is out of range for a tensor of %d dimensions", axis, x->n_dim);
-    axis_view v;
-    v.slot = dsc_axis_slot(x, axis);
-    v.n = x->shape[v.slot];
-    v.outer = v.inner = 1;
-    for (int i = 0; i < v.slot; ++i) v.outer *= x->shape[i];
-    for (int i = v.slot + 1; i < DSC_MAX_DIMS; ++i) v.inner *= x->shape[i];
-    return v;
-}
-
 // out of dtype odt and x's shape with n_out along the axis: allocated, or the caller's checked
-dsc_tensor *result_of(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, dsc_dtype odt, const axis_view &v, int n_out) {
+dsc_tensor *result_of(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, dsc_dtype odt, const dsc_axis_view &v, int n_out) {
     int out_shape[DSC_MAX_DIMS];
     memcpy(out_shape, x->shape, sizeof(out_shape));
     out_shape[v.slot] = n_out;
@@ -54,7 +40,7 @@ dsc_tensor *scan_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int ax
     DSC_ASSERT(x != nullptr);
     if (op == 1 && x->dtype != DSC_F32 && x->dtype != DSC_F64) DSC_LOG_FATAL("input must be real (f32 / f64)");
     if (op == 2 && x->dtype != DSC_C32 && x->dtype != DSC_C64) DSC_LOG_FATAL("input must be complex (c32 / c64)");
-    const axis_view v = view_of(x, axis);
+    const dsc_axis_view v = dsc_axis_view_of(x, axis);
     const dsc_dtype odt = op != 2 ? x->dtype : x->dtype == DSC_C32 ? DSC_F32 : DSC_F64;
     out = result_of(ctx, x, out, odt, v, v.n);
 
@@ -63,20 +49,11 @@ dsc_tensor *scan_impl(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int ax
         ctx->last_fft_path = "scan_cols";
         return out;
     }
-    bool tiles = v.outer < kTilesBelowRows && v.n > dsc_scan_tile_len(op, x->dtype);
-    if (const char *forced = getenv("DSC_SCAN_ROUTE")) {                 // read at every call: the tests and tools/bench_scan.py switch it
-        if (strcmp(forced, "rows") == 0) tiles = false;
-        else if (strcmp(forced, "tiles") == 0) tiles = true;
-        else DSC_LOG_FATAL("DSC_SCAN_ROUTE must be rows or tiles, got \"%s\"", forced);
-    }
-    if (tiles) {
+    const int forced = dsc_forced_route("DSC_SCAN_ROUTE", {"rows", "tiles"});
+    if (forced >= 0 ? forced == 1 : v.outer < kTilesBelowRows && v.n > dsc_scan_tile_len(op, x->dtype)) {
         const size_t need = dsc_scan_tiles_scratch_bytes(op, x->dtype, v.outer, v.n);
-        ctx->scratch.reset();
-        if (ctx->scratch.capacity() < need + DSC_DEVICE_ALIGN)
-            DSC_LOG_FATAL("scratch arena too small: the tile totals of %lld rows of %d need %.2f MB", v.outer, v.n, (double) need / 1048576.);
-        char *scratch = ctx->scratch.alloc(need);
-        dsc_launch_scan_tiles(x->data, out->data, op, x->dtype, v.outer, v.n, scratch, ctx->stream);
-        ctx->scratch.reset();                                            // the stream is in order: nothing reuses the block before the launches have read it
+        DSC_SCRATCH_BLOCK(scratch, ctx, need, "the tile totals of %lld rows of %d need %.2f MB", v.outer, v.n, (double) need / 1048576.);
+        dsc_launch_scan_tiles(x->data, out->data, op, x->dtype, v.outer, v.n, scratch.ptr, ctx->stream);
         ctx->last_fft_path = "scan_tiles";
     } else {
         dsc_launch_scan_rows(x->data, out->data, op, x->dtype, v.outer, v.n, ctx->stream);
@@ -105,7 +82,7 @@ extern "C" dsc_tensor *dsc_phase(dsc_ctx *ctx, const dsc_tensor *z, dsc_tensor *
 extern "C" dsc_tensor *dsc_diff(dsc_ctx *ctx, const dsc_tensor *x, dsc_tensor *out, int axis) {
     DSC_TRACE_OP(ctx, "op;unary", x, nullptr, 0, axis);
     DSC_ASSERT(x != nullptr);
-    const axis_view v = view_of(x, axis);
+    const dsc_axis_view v = dsc_axis_view_of(x, axis);
     if (v.n < 2) DSC_LOG_FATAL("the axis must have at least 2 elements, got %d", v.n);
     out = result_of(ctx, x, out, x->dtype, v, v.n - 1);
     dsc_launch_scan_diff(x->data, out->data, x->dtype, v.outer, v.n, v.inner, ctx->stream);

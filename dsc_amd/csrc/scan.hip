@@ -316,8 +316,6 @@ template<typename F> void with_scan_types(int op, int dtype, F f) {
     no_kernel("scan.hip", "operator and dtype", op * 10 + dtype);
 }
 
-size_t totals_bytes(long long n_seg, size_t elem) { return ((size_t) n_seg * elem + 255) & ~(size_t) 255; }
-
 }  // namespace
 
 int dsc_scan_tile_len(int op, int dtype) {
@@ -329,7 +327,7 @@ int dsc_scan_tile_len(int op, int dtype) {
 size_t dsc_scan_tiles_scratch_bytes(int op, int dtype, long long rows, int n) {
     const int tile_len = dsc_scan_tile_len(op, dtype);
     const long long n_seg = rows * ((n + tile_len - 1) / tile_len);
-    return 2 * totals_bytes(n_seg, 16);
+    return 2 * scratch_block_bytes(n_seg, 16);
 }
 
 void dsc_launch_scan_rows(const void *x, void *out, int op, int dtype, long long rows, int n, hipStream_t stream) {
@@ -350,7 +348,7 @@ void dsc_launch_scan_tiles(const void *x, void *out, int op, int dtype, long lon
         constexpr int tile_len = tile_len_of<OP, In>();
         const int tiles_per_row = (n + tile_len - 1) / tile_len;
         const long long n_seg = rows * tiles_per_row;
-        S *totals = (S *) scratch, *scanned = (S *) ((char *) scratch + totals_bytes(n_seg, 16));
+        S *totals = (S *) scratch, *scanned = (S *) ((char *) scratch + scratch_block_bytes(n_seg, 16));
         launch_seg<OP, In, true>((const In *) x, nullptr, nullptr, totals, n_seg, n, tile_len, tiles_per_row, stream);
         launch_seg<0, S, false>(totals, scanned, nullptr, nullptr, rows, tiles_per_row, tiles_per_row, 1, stream);
         launch_seg<OP, In, false>((const In *) x, (typename scan_types<OP, In>::Out *) out, scanned, nullptr, n_seg, n, tile_len, tiles_per_row, stream);

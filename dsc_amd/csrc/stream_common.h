@@ -1,6 +1,6 @@
-// stream_common.h — what the streaming kernel files (elementwise.hip, layout.hip, remap.hip, reduce.hip, scan.hip) share: the element
-// types behind the four dtype codes, the 16-byte pack, the capped streaming grid and the dtype and element-size tables of the dispatch.h
-// idiom.
+// stream_common.h — what the streaming kernel files (elementwise.hip, layout.hip, remap.hip, reduce.hip, scan.hip, moments.hip) share:
+// the element types behind the four dtype codes, the 16-byte pack, the capped streaming grid, the round-up of a scratch block and the
+// dtype and element-size tables of the dispatch.h idiom.
 // Everything sits in an anonymous namespace: cx and packed appear in kernel signatures, and each file keeps its own internal kernels.
 #pragma once
 
@@ -28,6 +28,9 @@ inline dim3 stream_grid(long long ne) {
     if (blocks < 1) blocks = 1;
     return dim3((unsigned) blocks);
 }
+
+// bytes of a scratch block of n elements, rounded up so that the block after it starts 256-byte aligned (scan.hip, moments.hip)
+inline size_t scratch_block_bytes(long long n, size_t elem) { return ((size_t) n * elem + 255) & ~(size_t) 255; }
 
 // dtype code (dsc_dtype: F32, F64, C32, C64) -> element type
 template<typename F> void with_dtype(int dtype, F f) {

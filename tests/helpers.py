@@ -76,6 +76,17 @@ def device_view(dsc, big, shape, dt):
     return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
 
 
+def assert_ends_the_process(stmt, message, without_env=None):
+    """`stmt` after dsc.init(1 << 28, 1 << 24) in a child process, the variable `without_env` taken out of its environment: a message
+    on stderr and exit status 1; nothing runs on the GPU after it."""
+    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
+    env = {k: v for k, v in os.environ.items() if k != without_env}
+    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
+    assert message in r.stderr, r.stderr[-400:]
+    assert 'HIP error' not in r.stderr and 'illegal memory' not in r.stderr
+
+
 class Golden:
     """Committed fixtures: outputs of the reference itself (tests/golden/make_golden.py)."""
 

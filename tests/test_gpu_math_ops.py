@@ -9,7 +9,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.helpers import GOLDEN, rel_l2
+from tests.helpers import GOLDEN, assert_ends_the_process, rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -282,6 +282,32 @@ def test_reshape_shares_the_buffer_and_frees_in_either_order(dsc):
             del x2
         v2 = dsc.reshape(x if first == 'view' else v, (2, 60))
         assert v2.shape == (2, 60) and np.array_equal(v2.numpy(), base.reshape(2, 60))
+
+
+def test_reductions_into_out_and_along_a_padding_axis(dsc):
+    """sum and max of f32 (2, 64) into a caller's out, the axis kept and dropped; the same along axis -3, which for a tensor of two
+    dimensions is a leading padding slot of extent 1 that the reductions accept, as the reference does: the result is x.  A
+    wrong-shaped out ends a child process with status 1.
+
+    Not run: axis -3 with the axis dropped.  The reference's shape rule then writes a fifth slot of its four-slot shape and asks for an
+    out of 2 elements that the 128 outputs of the launch would overrun; reduce.cpp refuses the call."""
+    x = _random((2, 64), np.float32, np.random.default_rng(23))
+    X = dsc.from_numpy(x)
+    for keep in (True, False):
+        shape = (2, 1) if keep else (2,)
+        out = dsc.empty(shape, dsc.Dtype.F32)
+        y = dsc.sum(X, out=out, axis=-1, keepdims=keep)
+        assert _data_ptr(y) == _data_ptr(out) and y.shape == shape
+        assert_matches(out.numpy(), x.astype(np.float64).sum(-1, keepdims=keep).astype(np.float32), *tolerance('sum', np.float32), what=f'sum keepdims={keep}')
+        out = dsc.empty(shape, dsc.Dtype.F32)
+        y = dsc.max(X, out=out, axis=-1, keepdims=keep)
+        assert _data_ptr(y) == _data_ptr(out) and np.array_equal(out.numpy(), x.max(-1, keepdims=keep))
+    for f in (dsc.sum, dsc.max):
+        out = dsc.empty((2, 64), dsc.Dtype.F32)
+        y = f(X, out=out, axis=-3, keepdims=True)
+        assert _data_ptr(y) == _data_ptr(out) and np.array_equal(out.numpy(), x), f.__name__
+        assert np.array_equal(f(X, axis=-3, keepdims=True).numpy(), x), f.__name__
+    assert_ends_the_process("dsc.sum(dsc.from_numpy(np.ones((2, 64), np.float32)), out=dsc.empty((2, 2), dsc.Dtype.F32), axis=-1)", 'shape')
 
 
 # ---- counterparts of the reference's python/tests/test_ops.py (test_binary 'power', test_unary, test_clip, test_arange,

@@ -26,18 +26,16 @@ near 1 are those.  In f64 / c64 the gamma terms allow n roundings in a row where
 ratios there come from axes of one to three elements."""
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.helpers import TOL, device_view
+from tests.helpers import TOL, assert_ends_the_process, device_view
 from tests.test_moments_abi import (C32, C64, F32, F64, LD, REAL_OF, Moments, build_cpp_moments_smoke, gamma, lay, moment_rows,
                                     reduced_shape)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 ROWS, TILES, COLS = 'rows', 'tiles', 'cols'
 DTYPES = [F32, F64, C32, C64]
 T_LAST = sorted({1, 2, 3, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097, 16383, 16384, 16385, 65535, 65537, 70001}
@@ -309,12 +307,7 @@ ERRORS = {
 def test_argument_errors_end_the_process(name):
     """like every operator: a message on stderr and exit status 1; nothing runs on the GPU after it"""
     stmt, message = ERRORS[name]
-    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
-    env = {k: v for k, v in os.environ.items() if k != 'DSC_MOMENT_ROUTE'}
-    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
-    assert message in r.stderr, r.stderr[-400:]
-    assert 'HIP error' not in r.stderr and 'illegal memory' not in r.stderr
+    assert_ends_the_process(stmt, message, without_env='DSC_MOMENT_ROUTE')
 
 
 def test_detrend_type_names(dsc):

@@ -9,17 +9,16 @@ processes."""
 import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.helpers import assert_ends_the_process
 from tests.test_remap_abi import (C32, C64, ELEMS, F32, F64, PACKS, PAD_MODES, ROWS, bits, build_cpp_remap_smoke, map_flip, map_identity, map_roll,
                                   pad_maps, random_bits, ref_fftshift, ref_flip, ref_ifftshift, ref_pad, ref_roll, route)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 DTYPES = [F32, F64, C32, C64]
 LENGTHS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 255, 256, 257, 1023, 1024, 1025, 4097)
 SENTINEL = -7.25
@@ -290,12 +289,7 @@ ERRORS = {
 def test_argument_errors_end_the_process(name):
     """like every operator: a message on stderr and exit status 1; nothing runs on the GPU after it"""
     stmt, message = ERRORS[name]
-    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\nX = dsc.from_numpy(np.ones((2, 64), np.float32))\n{stmt}\nprint('survived')\n"
-    env = {k: v for k, v in os.environ.items() if k != 'DSC_REMAP_ROUTE'}
-    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
-    assert message in r.stderr, r.stderr[-400:]
-    assert 'HIP error' not in r.stderr and 'illegal memory' not in r.stderr
+    assert_ends_the_process("X = dsc.from_numpy(np.ones((2, 64), np.float32))\n" + stmt, message, without_env='DSC_REMAP_ROUTE')
 
 
 def test_an_unknown_mode_name_is_a_python_error(dsc):

@@ -23,17 +23,16 @@ scan_tiles on the inner == 1 shapes.  Argument errors end the process and run in
 import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.helpers import assert_ends_the_process
 from tests.test_scan_abi import (C32, C64, F32, F64, UNIT, assert_away_from_ties, build_cpp_scan_smoke, cumsum_err, cumsum_rows,
                                  multi_wrap_rows, ref_unwrap, smooth_rows, unwrap_err, wrapped_chirps)
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 ROWS, TILES, COLS, DIFF = 'scan_rows', 'scan_tiles', 'scan_cols', 'scan_diff'
 # every length around a power of two up to 2^16, and 70001: the pack, wave, chunk and tile boundaries of every dtype lie among them
 T_LAST = sorted({t for k in range(17) for t in (2 ** k - 1, 2 ** k, 2 ** k + 1) if t >= 1} | {70001})
@@ -350,12 +349,7 @@ ERRORS = {
 def test_argument_errors_end_the_process(name):
     """like every operator: a message on stderr and exit status 1; nothing runs on the GPU after it"""
     stmt, message = ERRORS[name]
-    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
-    env = {k: v for k, v in os.environ.items() if k != 'DSC_SCAN_ROUTE'}
-    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
-    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
-    assert message in r.stderr, r.stderr[-400:]
-    assert 'HIP error' not in r.stderr and 'illegal memory' not in r.stderr
+    assert_ends_the_process(stmt, message, without_env='DSC_SCAN_ROUTE')
 
 
 def test_cpp_scan_smoke_on_the_gpu(tmp_path):

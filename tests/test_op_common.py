@@ -3,7 +3,11 @@
 A stand-alone host program includes the arithmetic part of the header alone (DSC_OP_COMMON_PURE: nothing but <cstddef>), reads queries
 from its standard input and prints the answers.  The expected values are the chunk formulas that stft.cpp, conv.cpp and hilbert.cpp each
 carried, and the rows-per-launch formulas of stft.cpp and conv.cpp, written out below from the source of the commit before the header
-existed.  Equality is exact."""
+existed.  Equality is exact.
+
+Likewise the rules of the axis operators: dsc_axis_view_on / dsc_axis_view_at against numpy's products around the axis,
+dsc_reduced_shape against numpy.sum's shape and against the block that reduce_entry (dsc_capi.cpp) and moments.cpp each carried, and
+dsc_route_index."""
 import os
 import subprocess
 
@@ -34,6 +38,25 @@ int main() {
                 if (rounded > n_lines) rounded = n_lines;
                 printf("%lld %lld\n", dsc_chunk_lines(capacity, fixed, line, reserve, n_lines), rounded);
             }
+        } else if (what == 'v') {     // s0 s1 s2 s3 n_dim axis: the view, slot n outer inner
+            int s[4], n_dim, axis;
+            if (scanf("%d %d %d %d %d %d", &s[0], &s[1], &s[2], &s[3], &n_dim, &axis) != 6) return 1;
+            const dsc_axis_view v = dsc_axis_view_on(s, n_dim, axis);
+            printf("%d %d %lld %lld\n", v.slot, v.n, v.outer, v.inner);
+        } else if (what == 's') {     // s0 s1 s2 s3 n_dim slot keep_dims: the reduced shape, rank and four slots, and the view at the slot
+            int s[4], n_dim, slot, keep, o[5] = {-7, -7, -7, -7, -7};
+            if (scanf("%d %d %d %d %d %d %d", &s[0], &s[1], &s[2], &s[3], &n_dim, &slot, &keep) != 7) return 1;
+            const int rank = dsc_reduced_shape(s, n_dim, slot, keep != 0, o);
+            if (o[4] != -7) return 2;
+            const dsc_axis_view v = dsc_axis_view_at(s, slot);
+            printf("%d %d %d %d %d %d %d %lld %lld\n", rank, o[0], o[1], o[2], o[3], v.slot, v.n, v.outer, v.inner);
+        } else if (what == 'n') {     // count value name...; "-" stands for the empty string
+            char value[32], names[4][32];
+            const char *list[4];
+            int count;
+            if (scanf("%d %31s", &count, value) != 2 || count > 4) return 1;
+            for (int i = 0; i < count; ++i) { if (scanf("%31s", names[i]) != 1) return 1; list[i] = names[i]; }
+            printf("%d\n", dsc_route_index(value[0] == '-' ? "" : value, list, count));
         } else {                      // limit row_bytes_in row_bytes_out rows odd_rows
             long long limit, in, out, rows;
             int odd;
@@ -176,3 +199,96 @@ def test_fused_rows_per_launch_is_the_two_formulas(program):
     got = program(queries)
     assert got.tolist() == want
     assert 1 in want and 0 in want and max(want) > 1000               # every kind of answer occurs
+
+
+# ---- the axis rules: a view along one axis, the shape of a reduction's result, a route name's index -------------------------------------
+
+EXTENTS = (1, 2, 3, 5)
+SHAPES = [s for n_dim in (1, 2, 3, 4) for s in np.ndindex(*(len(EXTENTS),) * n_dim)]
+SHAPES = [tuple(EXTENTS[i] for i in s) for s in SHAPES]
+
+
+def _slots(shape):
+    return (1,) * (4 - len(shape)) + tuple(shape)
+
+
+def _axis_slot(n_dim, axis):
+    """dsc_axis_slot (dsc_internal.h)"""
+    return 4 + axis if axis < 0 else 4 - n_dim + axis
+
+
+def test_axis_view_is_numpys_outer_n_inner(program):
+    """every rank, extents of 1, 2, 3 and 5, every axis from one below the valid range to one above it"""
+    queries, want = [], []
+    for shape in SHAPES:
+        n_dim = len(shape)
+        for axis in range(-n_dim - 1, n_dim + 1):
+            queries.append('v %d %d %d %d %d %d' % (_slots(shape) + (n_dim, axis)))
+            if -n_dim <= axis < n_dim:
+                a = axis % n_dim
+                want.append([_axis_slot(n_dim, axis), shape[a], int(np.prod(shape[:a], dtype=np.int64)), int(np.prod(shape[a + 1:], dtype=np.int64))])
+            else:
+                want.append([-1, 0, 0, 0])
+    got = program(queries).reshape(-1, 4)
+    assert got.tolist() == want
+    assert sum(w[0] == -1 for w in want) == 2 * len(SHAPES)
+
+
+def test_axis_view_refuses_a_rank_outside_1_to_4(program):
+    got = program(['v 1 1 1 1 0 0', 'v 1 1 1 1 0 -1', 'v 2 2 2 2 5 0', 'v 2 2 2 2 5 4', 'v 2 2 2 2 -1 0']).reshape(-1, 4)
+    assert got[:, 0].tolist() == [-1] * 5
+
+
+def reduce_entry_shape(slots, n_dim, slot, keep_dims):
+    """the keep-dims / drop-axis block of reduce_entry (dsc_capi.cpp) in the commit before the header had it"""
+    out_shape = [None] * 4
+    out_ndim = n_dim
+    if keep_dims:
+        out_shape = list(slots)
+        out_shape[slot] = 1
+    else:
+        out_ndim -= 1
+        lead = 4 - out_ndim
+        for i in range(lead):
+            out_shape[i] = 1
+        oi = 0
+        for xi in range(4 - n_dim, 4):
+            if xi == slot:
+                continue
+            out_shape[lead + oi] = slots[xi]
+            oi += 1
+    return [out_ndim] + out_shape
+
+
+def test_reduced_shape_is_numpys_and_reduce_entrys(program):
+    """the same sweep over the valid axes, times keep_dims; the view at the slot is the view along the axis"""
+    queries, cases = [], []
+    for shape in SHAPES:
+        n_dim = len(shape)
+        for axis in range(-n_dim, n_dim):
+            for keep in (0, 1):
+                queries.append('s %d %d %d %d %d %d %d' % (_slots(shape) + (n_dim, _axis_slot(n_dim, axis), keep)))
+                cases.append((shape, axis, keep))
+    got = program(queries).reshape(-1, 9).tolist()
+    for (shape, axis, keep), g in zip(cases, got):
+        n_dim, slot = len(shape), _axis_slot(len(shape), axis)
+        want = np.sum(np.empty(shape), axis, keepdims=bool(keep)).shape
+        rank, out_shape = g[0], g[1:5]
+        assert rank == len(want) and tuple(out_shape[4 - rank:]) == want and out_shape[:4 - rank] == [1] * (4 - rank), (shape, axis, keep, g)
+        assert g[:5] == reduce_entry_shape(_slots(shape), n_dim, slot, keep), (shape, axis, keep, g)
+        a = axis % n_dim
+        assert g[5:] == [slot, shape[a], int(np.prod(shape[:a], dtype=np.int64)), int(np.prod(shape[a + 1:], dtype=np.int64))]
+
+
+def test_reduced_shape_keeps_a_padding_slot(program):
+    """the reductions accept an axis in a leading padding slot with keep_dims: the shape as it is, a view of n = 1 around that slot"""
+    got = program(['s 1 1 2 64 2 1 1', 's 1 1 2 64 2 0 1']).reshape(-1, 9).tolist()
+    assert got == [[2, 1, 1, 2, 64, 1, 1, 1, 128], [2, 1, 1, 2, 64, 0, 1, 1, 128]]
+
+
+def test_route_index(program):
+    queries = ['n 2 rows rows tiles', 'n 2 tiles rows tiles', 'n 1 elems elems',       # known names
+               'n 2 fast rows tiles', 'n 1 rows elems',                                # unknown
+               'n 2 - rows tiles', 'n 1 - elems',                                      # the empty string
+               'n 2 row rows tiles', 'n 2 tile rows tiles', 'n 2 rowss rows tiles', 'n 1 e elems']      # a prefix of a name, a name as a prefix
+    assert program(queries).tolist() == [0, 1, 0, -1, -1, -1, -1, -1, -1, -1, -1]

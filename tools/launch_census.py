@@ -14,8 +14,10 @@
           context with 64 KiB of scratch, three chunks each.  Then the streaming files (elementwise, layout, reduce): one small call per
           branch of every launcher in them x the four dtypes — the five binary operators on every broadcast route and with operands of
           two dtypes, the unary functions, casts and arange at aligned, odd and 8-bytes-off-alignment counts, the four reductions on
-          every kernel, slices (get and set) and transposes per element size.  Prints one line per call,
-          'CALL ... <dsc.last_fft_path()>'.
+          every kernel, slices (get and set) and transposes per element size.  Then the axis operators (reduce, scan, moments, remap
+          .cpp) in a context of their own, f32 and c32: one small call per route of each family, chosen by shape and forced through
+          DSC_SCAN_ROUTE / DSC_MOMENT_ROUTE / DSC_REMAP_ROUTE.  Prints one line per call, 'CALL ... <dsc.last_fft_path()>'.
+--run axis  the axis operators' block alone.
 --compare the kernel-trace CSVs below the two directories in dispatch order: the same sequence of (Kernel_Name, Grid_Size, Workgroup_Size,
           LDS_Block_Size), and the same paths.txt.  Exits 1 on a difference.
 """
@@ -28,11 +30,16 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run():
+def run(only_axis=False):
     os.environ['DSC_NO_FUSED_L2'] = '1'
     sys.path.insert(0, ROOT)
     import numpy as np
     import dsc_amd as dsc
+    if only_axis:
+        dsc.init(2 << 30, 256 << 20)
+        axis_operators(dsc, np)
+        dsc.synchronize()
+        return
     dsc.init(10 << 30, 2 << 30)
     F32, F64, C64, C128 = np.float32, np.float64, np.complex64, np.complex128
     cpx = {F32: C64, F64: C128}
@@ -78,6 +85,10 @@ def run():
     dsc.shutdown()
     dsc.init(2 << 30, 256 << 20)
     streaming(dsc, np)
+    dsc.synchronize()
+    dsc.shutdown()
+    dsc.init(2 << 30, 256 << 20)
+    axis_operators(dsc, np)
     dsc.synchronize()
 
 
@@ -243,6 +254,49 @@ def streaming(dsc, np):
             call('transpose', lambda x: dsc.transpose(x, (2, 0, 1)), shape, dt)
 
 
+def axis_operators(dsc, np):
+    """reduce.cpp, scan.cpp, moments.cpp, remap.cpp: one small call per route, with the route the library reports after it (the
+    reductions report none: the line carries the call before them)"""
+    def call(what, fn, shape, dt, *note):
+        x = dsc.from_numpy(np.ones(shape, dtype=dt))
+        y = fn(x)
+        print('CALL', what, np.dtype(dt).name, shape, *note, dsc.last_fft_path(), flush=True)
+        del x, y
+
+    def along(name, axis, **kw):
+        return lambda x: getattr(dsc, name)(x, axis=axis, **kw)
+
+    for dt in (np.float32, np.complex64):
+        real = np.dtype(dt).kind == 'f'
+        turns = 'unwrap' if real else 'phase'
+        for name in ('sum', 'max'):                                 # row, row per wave, segmented, sequential, sequential in packs
+            for shape, axis in (((4, 64), 1), ((1024, 64), 1), ((256, 8), 0), ((30, 300), 0), ((2, 524288), 0)):
+                call(name, along(name, axis), shape, dt, axis)
+        for name in ('cumsum', turns):                              # tiles, rows, cols, then either forced on the other's shape
+            for shape, axis in (((3, 20000), 1), ((200, 300), 1), ((30, 300), 0)):
+                call(name, along(name, axis), shape, dt, axis)
+            for route, shape in (('rows', (3, 20000)), ('tiles', (200, 300))):
+                with switch('DSC_SCAN_ROUTE', route):
+                    call(name, along(name, 1), shape, dt, route)
+        call('diff', along('diff', 1), (3, 1001), dt, 1)
+        call('diff', along('diff', 0), (30, 300), dt, 0)
+        moments = (('sumsq', {}), ('var', {}), ('vdot', {}), ('detrend', {'type': 'linear'}))
+        for name, kw in moments:                                    # rows by workgroup and by wave, tiles, cols, cols in segments
+            fn = (lambda axis: lambda x: dsc.vdot(x, x, axis=axis)) if name == 'vdot' else (lambda axis: along(name, axis, **kw))
+            for shape, axis in (((4, 64), 1), ((1024, 64), 1), ((3, 20000), 1), ((30, 300), 0), ((256, 8), 0)):
+                call(name, fn(axis), shape, dt, axis)
+            for route, shape in (('rows', (3, 20000)), ('tiles', (1024, 64))):
+                with switch('DSC_MOMENT_ROUTE', route):
+                    call(name, fn(1), shape, dt, route)
+        call('flip', along('flip', 0), (8, 64), dt, 0)              # rows, packs, elems, elems forced
+        call('flip', along('flip', 1), (8, 64), dt, 1)
+        call('flip', along('flip', 1), (3, 5), dt, 1)
+        with switch('DSC_REMAP_ROUTE', 'elems'):
+            call('flip', along('flip', 0), (8, 64), dt, 'elems')
+        call('roll', lambda x: dsc.roll(x, 3), (8, 64), dt, 'axis=None')
+        call('pad', lambda x: dsc.pad(x, ((1, 2), (3, 4))), (8, 64), dt, 'constant')
+
+
 def trace(d):
     files = sorted(glob.glob(os.path.join(d, '**', '*kernel_trace.csv'), recursive=True))
     if len(files) != 1:
@@ -272,8 +326,8 @@ def compare(a, b):
 
 
 if __name__ == '__main__':
-    if sys.argv[1:] == ['--run']:
-        run()
+    if sys.argv[1:] in (['--run'], ['--run', 'axis']):
+        run(only_axis=len(sys.argv) == 3)
     elif len(sys.argv) == 4 and sys.argv[1] == '--compare':
         compare(sys.argv[2], sys.argv[3])
     else:
