@@ -3,6 +3,7 @@
 //                                        its own with_..._len table next to its supports() gate, and ends it with no_kernel
 //   with_index<N>                        the same for a code 0 .. N - 1 (operator codes); with_dtype is in stream_common.h
 //   dsc_launch_dyn_lds / dsc_launch_var_lds   the one place that opts a kernel in to its dynamic LDS (once per device) and launches it
+//   dsc_grid_for                         grid size of the grid-stride helper kernels
 //   dsc_cu_count                         grid size of the persistent kernels
 #pragma once
 
@@ -60,6 +61,12 @@ static inline void dsc_launch_dyn_lds(dim3 grid, dim3 block, size_t lds, hipStre
     if (dsc_first_use_on_device(seen))
         DSC_KERNEL_CHECK(hipFuncSetAttribute((const void *) Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds));
     DSC_LAUNCH(Kernel, grid, block, lds, stream, args...);
+}
+
+// blocks of `threads` for `items` work items of a grid-stride kernel: at least 1, at most 65536
+static inline unsigned dsc_grid_for(long long items, int threads) {
+    const long long blocks = (items + threads - 1) / threads;
+    return (unsigned) (blocks < 65536 ? (blocks > 0 ? blocks : 1) : 65536);
 }
 
 // compute units of the current device (asked once per device): the grid of a persistent kernel

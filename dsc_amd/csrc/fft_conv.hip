@@ -4,7 +4,7 @@
 //                        samples [D, n), which go to y[row][b hop + j - D] where that is < T_out.  Every output sample is written once.
 //                        (The fused route does the same in the store of the filter kernel, fft_regs_mid.hip.)
 //   reverse_kernel       h reversed, for dsc_correlate.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,11 +30,6 @@ __global__ __launch_bounds__(kThreads) void reverse_kernel(const R *__restrict__
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads) out[i] = in[n - 1 - i];
 }
 
-unsigned grid_for(long long total) {
-    const long long blocks = (total + kThreads - 1) / kThreads;
-    return (unsigned) (blocks < 65536 ? (blocks > 0 ? blocks : 1) : 65536);
-}
-
 }  // namespace
 
 void dsc_launch_conv_crop(const void *frames, void *y, long long q0, long long n_lines, int n, int D, int n_blocks, long long T_out,
@@ -42,18 +37,17 @@ void dsc_launch_conv_crop(const void *frames, void *y, long long q0, long long n
     const int hop = n - D;
     const long long total = n_lines * hop;
     if (total <= 0) return;
-    if (single_precision)
-        DSC_LAUNCH(conv_crop_kernel<float>, dim3(grid_for(total)), dim3(kThreads), 0, stream, (const float *) frames, (float *) y, q0, total, n,
-                   D, hop, n_blocks, T_out);
-    else
-        DSC_LAUNCH(conv_crop_kernel<double>, dim3(grid_for(total)), dim3(kThreads), 0, stream, (const double *) frames, (double *) y, q0, total,
-                   n, D, hop, n_blocks, T_out);
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        DSC_LAUNCH(conv_crop_kernel<R>, dim3(dsc_grid_for(total, kThreads)), dim3(kThreads), 0, stream, (const R *) frames, (R *) y, q0, total, n, D, hop,
+                   n_blocks, T_out);
+    });
 }
 
 void dsc_launch_reverse(const void *in, void *out, int n, bool single_precision, hipStream_t stream) {
     if (n <= 0) return;
-    if (single_precision)
-        DSC_LAUNCH(reverse_kernel<float>, dim3(grid_for(n)), dim3(kThreads), 0, stream, (const float *) in, (float *) out, n);
-    else
-        DSC_LAUNCH(reverse_kernel<double>, dim3(grid_for(n)), dim3(kThreads), 0, stream, (const double *) in, (double *) out, n);
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        DSC_LAUNCH(reverse_kernel<R>, dim3(dsc_grid_for(n, kThreads)), dim3(kThreads), 0, stream, (const R *) in, (R *) out, n);
+    });
 }

@@ -11,7 +11,7 @@
 //
 // They stream in 16-byte packs, like elementwise.hip: a thread takes 4 f32 / 2 f64 samples of y and of x and stores one pack of moduli or
 // two packs of complex pairs.  Rows of x whose pitch or base is not 16-byte aligned, and the last incomplete pack, go sample by sample.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -116,11 +116,6 @@ __global__ __launch_bounds__(kThreads) void hilbert_zip_kernel(const R *__restri
     }
 }
 
-unsigned grid_for(long long items) {
-    const long long blocks = (items + kThreads - 1) / kThreads;
-    return (unsigned) (blocks < 65536 ? (blocks > 0 ? blocks : 1) : 65536);
-}
-
 // xw [n_lines][wpitch] doubles <- samples j < in_len of rows q0 .. of x [..][in_pitch] floats, zero at j >= in_len; wpitch even: one 16-byte
 // pack of two doubles per thread
 __global__ __launch_bounds__(kThreads) void hilbert_widen_kernel(const float *__restrict__ x, double *__restrict__ xw, long long q0, long long pairs,
@@ -137,33 +132,23 @@ __global__ __launch_bounds__(kThreads) void hilbert_widen_kernel(const float *__
     }
 }
 
-template<typename R, typename YR, bool ENV>
-void launch_zip(const void *x, const void *y, void *out, long long q0, long long total, int logn, long long in_pitch, int in_len, hipStream_t stream) {
-    constexpr int P = 16 / (int) sizeof(R);
-    const bool vec = ((uintptr_t) x & 15) == 0 && ((uintptr_t) out & 15) == 0 && in_pitch % P == 0 && (q0 << logn) % P == 0;
-    const unsigned grid = grid_for((total + P - 1) / P);
-    if (vec)
-        DSC_LAUNCH((hilbert_zip_kernel<R, YR, ENV, true>), dim3(grid), dim3(kThreads), 0, stream, (const R *) x, (const YR *) y, (R *) out, q0, total, logn,
-                   in_pitch, in_len);
-    else
-        DSC_LAUNCH((hilbert_zip_kernel<R, YR, ENV, false>), dim3(grid), dim3(kThreads), 0, stream, (const R *) x, (const YR *) y, (R *) out, q0, total, logn,
-                   in_pitch, in_len);
-}
-
 }  // namespace
 
 void dsc_launch_hilbert_response(void *H, int n, bool single_precision, hipStream_t stream) {
     const int bins = n / 2 + 1;
-    if (single_precision) DSC_LAUNCH(hilbert_response_kernel<float>, dim3(grid_for((bins + 1) / 2)), dim3(kThreads), 0, stream, (float *) H, bins);
-    else                  DSC_LAUNCH(hilbert_response_kernel<double>, dim3(grid_for(bins)), dim3(kThreads), 0, stream, (double *) H, bins);
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        constexpr int P = 8 / (int) sizeof(R);                          // bins per pack
+        DSC_LAUNCH(hilbert_response_kernel<R>, dim3(dsc_grid_for((bins + P - 1) / P, kThreads)), dim3(kThreads), 0, stream, (R *) H, bins);
+    });
 }
 
 void dsc_launch_hilbert_widen(const void *x, void *xw, long long q0, long long n_lines, long long in_pitch, int in_len, int wpitch,
                               hipStream_t stream) {
     const long long pairs = n_lines * (wpitch / 2);
     if (pairs <= 0) return;
-    DSC_LAUNCH(hilbert_widen_kernel, dim3(grid_for(pairs)), dim3(kThreads), 0, stream, (const float *) x, (double *) xw, q0, pairs, wpitch / 2, in_pitch,
-               in_len);
+    DSC_LAUNCH(hilbert_widen_kernel, dim3(dsc_grid_for(pairs, kThreads)), dim3(kThreads), 0, stream, (const float *) x, (double *) xw, q0, pairs, wpitch / 2,
+               in_pitch, in_len);
 }
 
 void dsc_launch_hilbert_zip(const void *x, const void *y, void *out, long long q0, long long n_lines, int n, long long in_pitch, int in_len,
@@ -172,14 +157,19 @@ void dsc_launch_hilbert_zip(const void *x, const void *y, void *out, long long q
     if (total <= 0) return;
     int logn = 0;
     while ((1 << logn) < n) ++logn;
-    if (single_precision && y_double) {
-        if (envelope) launch_zip<float, double, true>(x, y, out, q0, total, logn, in_pitch, in_len, stream);
-        else          launch_zip<float, double, false>(x, y, out, q0, total, logn, in_pitch, in_len, stream);
-    } else if (single_precision) {
-        if (envelope) launch_zip<float, float, true>(x, y, out, q0, total, logn, in_pitch, in_len, stream);
-        else          launch_zip<float, float, false>(x, y, out, q0, total, logn, in_pitch, in_len, stream);
-    } else {
-        if (envelope) launch_zip<double, double, true>(x, y, out, q0, total, logn, in_pitch, in_len, stream);
-        else          launch_zip<double, double, false>(x, y, out, q0, total, logn, in_pitch, in_len, stream);
-    }
+    // (R, YR): y is of R's type, or double under f32 rows when y_double is set (never float under f64 rows)
+    auto launch = [&](auto real, auto yreal) { with_bool(envelope, [&](auto env) {
+        using R = decltype(real);
+        using YR = decltype(yreal);
+        constexpr int P = 16 / (int) sizeof(R);
+        const bool vec = ((uintptr_t) x & 15) == 0 && ((uintptr_t) out & 15) == 0 && in_pitch % P == 0 && (q0 << logn) % P == 0;
+        with_bool(vec, [&](auto v) {
+            DSC_LAUNCH((hilbert_zip_kernel<R, YR, decltype(env)::value, decltype(v)::value>), dim3(dsc_grid_for((total + P - 1) / P, kThreads)), dim3(kThreads), 0,
+                       stream, (const R *) x, (const YR *) y, (R *) out, q0, total, logn, in_pitch, in_len);
+        });
+    }); };
+    with_real(single_precision, [&](auto real) {
+        if constexpr (sizeof(real) == 4) { if (y_double) return launch(real, double{}); }
+        launch(real, real);
+    });
 }

@@ -54,7 +54,6 @@ template<typename R, int B, bool TWO, int CW> struct cols_cfg {
     static constexpr int TABLE = TWO ? L : 1024;       // W_L^m (two-pass) or W_1024^m
     static constexpr int TABLE_STRIDE = TWO ? 1 : B;
     static constexpr int WAVES_PER_EU = NT >= 1024 ? 4 : sizeof(R) == 8 ? 2 : NT >= 512 ? 4 : 2;
-    static constexpr bool PIPE = false;                // persistent, software-pipelined tile loop (three-pass forms): measured, off
 };
 template<typename R, int B, bool TWO, int CW>
 constexpr size_t cols_lds_bytes() { return ((size_t) cols_cfg<R, B, TWO, CW>::PLANE + 2 * cols_cfg<R, B, TWO, CW>::TABLE) * sizeof(R); }
@@ -142,13 +141,19 @@ __device__ __forceinline__ void cols_passes(cpx<R> (&v)[32], R *plane, const cpx
 // otherwise; the rest of the transform length reads as zero: dsc.cpp:1990-1998, 2125-2133, 2149-2157) and a pitch of `inner`
 // elements between consecutive elements; in_axis / out_axis = the axis lengths of the two tensors (slice pitch = axis * inner).
 //
-// Round 3.  (1) The three-pass forms (L = 2048, 4096: one workgroup fills a CU) are PERSISTENT and software pipelined like the
-// 65536-point kernels: a workgroup walks tiles blockIdx.x, + gridDim.x, ...; the next tile's loads are issued into registers
-// the current tile has finished with, ahead of (half of) its stores, so that a CU's load, compute and store phases overlap.
-// (2) The inverse packed-real pre-pass handles every pair (k, L - k) ONCE: a thread loads its lower 16 bins AND their partners
-// (rows L - k: the same 32 row loads as its own upper half), computes Z[k] and Z[L - k] together and hands Z[L - k] to its owner
-// through the staging plane — half the arithmetic, one exchange instead of two, and no second 32-value array (the old form
-// spilled 14 - 35 registers).
+// One workgroup per tile of CW columns, one tile per workgroup.  The packed-real passes come in two forms, chosen by the line length:
+//   32-point lines (T == 1, one thread per column): both partners of every pair (k, L - k) live in the thread.  The inverse pre-pass
+//       runs in registers, without staging or barrier; the forward post-pass sends both halves through the staging plane, one
+//       component at a time (two exchanges).
+//   64 points and more (T >= 2): only the upper halves travel through the staging plane, once, and every pair is computed once
+//       (fft_regs_mid.hip, "who owns which bin": thread t of a column holds the bins t + T m, its partners L - k are upper bins of
+//       thread T - t of the same column) — the inverse pre-pass and the forward post-pass alike.
+// Measured in round 3 and not kept: a persistent, software-pipelined tile loop for the three-pass forms (the next tile's loads ahead
+// of half of the stores) measured 0.648 against 0.584 ms on 2048-point c32 lines and 1.27 against 1.13 ms on 4096-point ones: these
+// tiles are limited by the size of their pieces (16 / 8 columns = 128 / 64 B per row), not by the overlap of their phases
+// (profiles/r03_cols_axis0.md, section 1).  An f32 inverse pre-pass that loads the partners L - k from memory measured equal or worse
+// than the one-exchange form — irfft along axis 0, 1024 points 63.1 against 65.3 % of the roofline, 512: 67.0 against 67.8 % — and
+// the two-exchange pre-pass for T >= 2 spilled 6 - 35 registers (the same note, sections 2 and 5).
 template<typename R, int B, bool TWO, int CW, int MODE, bool INV>
 __global__ __launch_bounds__((cols_cfg<R, B, TWO, CW>::NT), (cols_cfg<R, B, TWO, CW>::WAVES_PER_EU)) void fft_cols_kernel(
     const void *__restrict__ in, void *__restrict__ out, int inner, int tiles_per_slice, int n_tiles, int in_axis, int in_len, int out_axis,
@@ -160,395 +165,237 @@ __global__ __launch_bounds__((cols_cfg<R, B, TWO, CW>::NT), (cols_cfg<R, B, TWO,
     constexpr int IB = (MODE == DSC_MODE_R2C_PACKED || MODE == DSC_MODE_R2C_CAST) ? RB : CB;       // bytes per input element
     constexpr int OB = MODE == DSC_MODE_C2R_PACKED ? RB : CB;       // bytes per output element
     constexpr int kOut = 0x7f000000;                                // an offset past every descriptor range: reads 0, stores dropped
-    // PIPE: persistent + next tile requested ahead of the stores.  Built and measured in round 3 (profiles/r03_cols_axis0.md): it does
-    // not pay — 2048-point c32 lines 0.648 ms against 0.584 ms, 4096-point 1.27 against 1.13 — because these tiles are not limited by
-    // the overlap of their phases but by the size of their pieces (16 / 8 columns = 128 / 64 B per row of the tensor); kept, off.
-    constexpr bool PIPE = cfg::PIPE && !TWO;
-    // the inverse pre-pass with every pair handled once (see above): the f32 forms lose their spills with it (14 - 25 -> 0 - 4),
-    // the f64 forms get more (6 - 35 -> 19 - 54: hipcc starts all sixteen pairs at once), so they keep the two-exchange form
-    // (later in round 3: the one-exchange pre-pass below needs no second set of loads and measured equal or better — irfft along axis 0,
-    // 1024 points 63.1 -> 65.3 %, 512: 67.0 -> 67.8 %, the others within 0.3 points (tools/r03_call_aa.sh) — so the form that loads the
-    // partners from memory is off; -DDSC_COLS_PAIR_ONCE brings it back for f32)
-#ifdef DSC_COLS_PAIR_ONCE
-    constexpr bool PAIR_ONCE = sizeof(R) == 4;
-#else
-    constexpr bool PAIR_ONCE = false;
-#endif
-    // The real passes that move only the upper halves through the staging plane (fft_regs_mid.hip, "who owns which bin": thread t of a
-    // column holds the bins t + T m, its partners L - k are upper bins of thread T - t of the same column): forward post-pass and, where
-    // PAIR_ONCE is off, the inverse pre-pass.
-#ifdef DSC_COLS_OLD_REAL_PASSES
-    constexpr bool POST_ONCE = false, PRE_ONCE = false;
-#else
-    constexpr bool POST_ONCE = T >= 2 && !PIPE, PRE_ONCE = T >= 2;
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
     R *plane = (R *) lds_raw;
     C *wtab = (C *) (plane + cfg::PLANE);
 
     for (int i = threadIdx.x; i < cfg::TABLE; i += NT) wtab[i] = tw_full[(long long) i * cfg::TABLE_STRIDE];
-    // Everything derived from the thread id is loop invariant: hipcc hoists it out of the persistent loop (dozens of addresses) and
-    // then spills.  Each phase therefore rebuilds (t, c) from an opaque copy of the id, so that nothing outlives its phase.
-    auto tid_now = [&]() { int x = (int) threadIdx.x; if constexpr (PIPE) asm volatile("" : "+v"(x)); return x; };
 
-    // descriptor of a tile's input slice (wave uniform) and a lane's column in it; a tile past the end reads zeros
-    auto in_rsrc = [&](int tile) {
+    const int tile = blockIdx.x;
+    // Each phase below rebuilds the slice, (t, c) and the column from blockIdx.x / threadIdx.x instead of sharing one set of locals, and
+    // the stores go through a lambda: with the locals hoisted or the lambdas unrolled by hand hipcc orders the instructions of 18 to 90
+    // of this file's 110 kernels differently (profiles/variants_refactor.md), which makes either a change to measure.
+    // descriptor of the tile's input slice (wave uniform; a tile past the end reads zeros) and a lane's column in the slice
+    auto in_rsrc = [&]() {
         const int slice = tile / tiles_per_slice;
         return __builtin_amdgcn_make_buffer_rsrc((void *) ((const char *) in + (size_t) slice * in_axis * inner * IB), 0, tile < n_tiles ? in_len * inner * IB : 0, 0x00020000);
     };
-    auto col_of = [&](int tile, int c) { return (tile - (tile / tiles_per_slice) * tiles_per_slice) * CW + c; };
-    // the loads of one tile, rows [J0, J0 + N) of the 32 a thread holds (see the modes below); C2R: dst[j] = Y[T j + t] for j < 16,
-    // dst[16 + j] = its partner Y[L - T j - t]
-    auto request = [&](auto &dst, auto j0_tag, auto n_tag, int tile) {
-        constexpr int J0 = decltype(j0_tag)::value, N = decltype(n_tag)::value;
-        const __amdgpu_buffer_rsrc_t rin = in_rsrc(tile);
-        const int tid = tid_now(), c = tid % CW, t = tid / CW;
-        const int col = col_of(tile, c);
+    auto col_of = [&](int c) { return (tile - (tile / tiles_per_slice) * tiles_per_slice) * CW + c; };
+    // the loads of the tile: the 32 rows a thread holds (see the modes above)
+    auto request = [&](C (&dst)[32]) {
+        const __amdgpu_buffer_rsrc_t rin = in_rsrc();
+        const int tid = (int) threadIdx.x, c = tid % CW, t = tid / CW;
+        const int col = col_of(c);
         const bool live = col < inner;
         if constexpr (MODE == DSC_MODE_R2C_PACKED) {                // z[m] = (x[2m], x[2m + 1]): two rows of the axis
             const int voff = live ? (2 * t * inner + col) * RB : kOut;
             const int row_b = inner * RB, step = 2 * T * inner * RB;
 #pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const cpx<R> a = buf_load_real<kStream>(rin, voff, (J0 + j) * step, R{}), b = buf_load_real<kStream>(rin, voff, (J0 + j) * step + row_b, R{});
+            for (int j = 0; j < 32; ++j) {
+                const cpx<R> a = buf_load_real<kStream>(rin, voff, j * step, R{}), b = buf_load_real<kStream>(rin, voff, j * step + row_b, R{});
                 dst[j] = C{a.x, b.x};
             }
         } else if constexpr (MODE == DSC_MODE_R2C_CAST) {           // dsc_fft / dsc_ifft of a real tensor: widened while loading
             const int voff = live ? (t * inner + col) * RB : kOut;
             const int step = T * inner * RB;
 #pragma unroll
-            for (int j = 0; j < N; ++j) dst[j] = buf_load_real<kStream>(rin, voff, (J0 + j) * step, R{});
-        } else if constexpr (MODE == DSC_MODE_C2R_PACKED && PAIR_ONCE) {
-            const int step = T * inner * CB;
-            const int voff_k = live ? (t * inner + col) * CB : kOut;
-            const int voff_m = live ? (((L - 15 * T) - t) * inner + col) * CB : kOut;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                const int jj = J0 + j;
-                dst[j] = jj < 16 ? buf_load<kStream>(rin, voff_k, jj * step, R{}) : buf_load<kStream>(rin, voff_m, (31 - jj) * step, R{});
-            }
+            for (int j = 0; j < 32; ++j) dst[j] = buf_load_real<kStream>(rin, voff, j * step, R{});
         } else {
             const int voff = live ? (t * inner + col) * CB : kOut;
             const int step = T * inner * CB;
 #pragma unroll
-            for (int j = 0; j < N; ++j) dst[j] = buf_load<kStream>(rin, voff, (J0 + j) * step, R{});
+            for (int j = 0; j < 32; ++j) dst[j] = buf_load<kStream>(rin, voff, j * step, R{});
         }
     };
-    auto request_mid = [&](int tile) {                              // C2R, thread 0 of a column: bin L/2, which pairs with itself (two-exchange form: bin L)
+    auto request_mid = [&]() {                                      // C2R, thread 0 of a column: bin L
         C y = C{(R) 0, (R) 0};
-        const int tid = tid_now(), c = tid % CW, t = tid / CW;
+        const int tid = (int) threadIdx.x, c = tid % CW, t = tid / CW;
         if (MODE == DSC_MODE_C2R_PACKED && t == 0) {
-            const int col = col_of(tile, c);
-            y = buf_load<kStream>(in_rsrc(tile), col < inner ? col * CB : kOut, (PAIR_ONCE ? L / 2 : L) * inner * CB, R{});
+            const int col = col_of(c);
+            y = buf_load<kStream>(in_rsrc(), col < inner ? col * CB : kOut, L * inner * CB, R{});
         }
         return y;
     };
-    using i0 = std::integral_constant<int, 0>;
-    using i16 = std::integral_constant<int, 16>;
-    using i32 = std::integral_constant<int, 32>;
 
-    // C2R: the pre-pass twiddle of this thread, requested FIRST — arriving after the data it lets hipcc start all sixteen pairs
-    // (their sums and differences) and hold them until it is there: 40 - 90 spilled registers
+    // f32 C2R: a load of this thread's pre-pass twiddle that nothing reads any more (the removed pre-pass that loaded the partners from
+    // memory did); the asm keeps it alive, and it stays so that this commit changes no device code.  Removing it is a change to measure.
     C wpre = C{(R) 0, (R) 0};
     if constexpr (MODE == DSC_MODE_C2R_PACKED && sizeof(R) == 4) {
-        wpre = tw_real[tid_now() / CW];
+        wpre = tw_real[(int) threadIdx.x / CW];
         asm volatile("" : "+v"(wpre.x), "+v"(wpre.y));
     }
     C v[32];
-    request(v, i0{}, i32{}, (int) blockIdx.x);
-    C ymid = C{(R) 0, (R) 0};
-    if constexpr (PAIR_ONCE) ymid = request_mid((int) blockIdx.x);
-    if constexpr (PIPE) __syncthreads();                            // twiddle table visible (one-tile forms: at the barrier after the pre-pass,
-                                                                    // so that the loads are not all waited for at once)
-    int tile = blockIdx.x;
-    do {                                                            // one tile unless PIPE
-        const int next = PIPE ? tile + (int) gridDim.x : n_tiles;
-        const int slice = tile / tiles_per_slice;
-        // (plain calls: group = 1, out_pitch = inner — slice * out_axis * inner elements, a range of out_axis * inner)
-        const size_t out_base = (size_t) (slice / rm.group) * out_axis * rm.out_pitch + (size_t) (slice % rm.group) * inner;
-        const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
-            (void *) ((char *) out + out_base * OB), 0, ((out_axis - 1) * rm.out_pitch + inner) * OB, 0x00020000);
+    request(v);
+    const int slice = tile / tiles_per_slice;
+    // (plain calls: group = 1, out_pitch = inner — slice * out_axis * inner elements, a range of out_axis * inner)
+    const size_t out_base = (size_t) (slice / rm.group) * out_axis * rm.out_pitch + (size_t) (slice % rm.group) * inner;
+    const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc(
+        (void *) ((char *) out + out_base * OB), 0, ((out_axis - 1) * rm.out_pitch + inner) * OB, 0x00020000);
 
-        if constexpr (MODE == DSC_MODE_C2R_PACKED && !PAIR_ONCE && T == 1) {
-            // 32-point lines, one thread per column: both partners of every pair live in this thread — no staging, no barrier.
-            // (k, L - k) = (j, 32 - j): a = v[j], b = v[32 - j]; W_2L^j = W_64^j, a compile-time constant.
-            const C yl = request_mid(tile);                         // bin L
-            { const R a = v[0].x, b = yl.x; v[0] = C{(R) 0.5 * (a + b), (R) 0.5 * (a - b)}; }       // bins 0 and L: real parts only (dsc_fft.h:227-232)
+    if constexpr (MODE == DSC_MODE_C2R_PACKED && T == 1) {
+        // 32-point lines, one thread per column: both partners of every pair live in this thread — no staging, no barrier.
+        // (k, L - k) = (j, 32 - j): a = v[j], b = v[32 - j]; W_2L^j = W_64^j, a compile-time constant.
+        const C yl = request_mid();                             // bin L
+        { const R a = v[0].x, b = yl.x; v[0] = C{(R) 0.5 * (a + b), (R) 0.5 * (a - b)}; }       // bins 0 and L: real parts only (dsc_fft.h:227-232)
 #pragma unroll
-            for (int j = 1; j < 16; ++j) {
-                const R wqx = (R) (0.5 * root64_im(j)), wqy = (R) (0.5 * root64_re(j));             // wq = (i/2) conj(W_64^j)
-                const C a = v[j], b = v[32 - j];
-                const R sx = (R) 0.5 * (a.x + b.x), sy = (R) 0.5 * (a.y - b.y), dx = a.x - b.x, dy = a.y + b.y;
-                const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
-                v[j] = C{sx + wdx, sy + wdy};
-                v[32 - j] = C{sx - wdx, wdy - sy};
-            }
-            v[16].y = -v[16].y;                                     // Z[L/2] = conj Y[L/2]
+        for (int j = 1; j < 16; ++j) {
+            const R wqx = (R) (0.5 * root64_im(j)), wqy = (R) (0.5 * root64_re(j));             // wq = (i/2) conj(W_64^j)
+            const C a = v[j], b = v[32 - j];
+            const R sx = (R) 0.5 * (a.x + b.x), sy = (R) 0.5 * (a.y - b.y), dx = a.x - b.x, dy = a.y + b.y;
+            const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
+            v[j] = C{sx + wdx, sy + wdy};
+            v[32 - j] = C{sx - wdx, wdy - sy};
         }
-        if constexpr (MODE == DSC_MODE_C2R_PACKED && !PAIR_ONCE && T != 1 && PRE_ONCE) {
-            // pair (k, L - k), k = t + T j, j < 16: a = Y[k] (own), b = Y[L-k] = an upper bin of thread T - t; the upper halves go to the
-            // staging plane (slot of bin b: b - L/2; x plane rows [0, L/2), y plane [L/2, L)), one barrier, every pair is computed once,
-            // Z[L-k] goes back into the slot b came from (this thread is its only reader), second barrier, everybody collects its upper half
-            const int tid = tid_now(), c = tid % CW, t = tid / CW;
-            R *stage = plane + c;
-            const C wbase = tw_real[t];
-            C yl = request_mid(tile);                               // bin L (thread 0)
-            if (t == 0) { v[0].y = (R) 0; yl.y = (R) 0; }           // bins 0 and L: real parts only (dsc_fft.h:227-228)
-            R *own_x = stage + t * CW, *own_y = own_x + (L / 2) * CW;
-            R *par_x = stage + ((L / 2 - 15 * T) - t) * CW, *par_y = par_x + (L / 2) * CW;
+        v[16].y = -v[16].y;                                     // Z[L/2] = conj Y[L/2]
+    }
+    if constexpr (MODE == DSC_MODE_C2R_PACKED && T >= 2) {
+        // pair (k, L - k), k = t + T j, j < 16: a = Y[k] (own), b = Y[L-k] = an upper bin of thread T - t; the upper halves go to the
+        // staging plane (slot of bin b: b - L/2; x plane rows [0, L/2), y plane [L/2, L)), one barrier, every pair is computed once,
+        // Z[L-k] goes back into the slot b came from (this thread is its only reader), second barrier, everybody collects its upper half
+        const int tid = (int) threadIdx.x, c = tid % CW, t = tid / CW;
+        R *stage = plane + c;
+        const C wbase = tw_real[t];
+        C yl = request_mid();                                   // bin L (thread 0)
+        if (t == 0) { v[0].y = (R) 0; yl.y = (R) 0; }           // bins 0 and L: real parts only (dsc_fft.h:227-228)
+        R *own_x = stage + t * CW, *own_y = own_x + (L / 2) * CW;
+        R *par_x = stage + ((L / 2 - 15 * T) - t) * CW, *par_y = par_x + (L / 2) * CW;
 #pragma unroll
-            for (int j = 16; j < 32; ++j) { own_x[T * (j - 16) * CW] = v[j].x; own_y[T * (j - 16) * CW] = v[j].y; }
-            if (t == 0) own_y[0] = -v[16].y;                        // bin L/2 pairs with itself: Z[L/2] = conj Y[L/2]
-            lds_barrier();
+        for (int j = 16; j < 32; ++j) { own_x[T * (j - 16) * CW] = v[j].x; own_y[T * (j - 16) * CW] = v[j].y; }
+        if (t == 0) own_y[0] = -v[16].y;                        // bin L/2 pairs with itself: Z[L/2] = conj Y[L/2]
+        lds_barrier();
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const C a = v[j];
-                C b = C{par_x[T * (15 - j) * CW], par_y[T * (15 - j) * CW]};
-                if (j == 0 && t == 0) b = yl;
-                const C w = cmul(wbase, C{(R) root64_re(j), (R) root64_im(j)});        // W_2L^{t + T j} = W_2L^t W_64^j
-                const R wqx = (R) 0.5 * w.y, wqy = (R) 0.5 * w.x;
-                const R sx = (R) 0.5 * (a.x + b.x), sy = (R) 0.5 * (a.y - b.y), dx = a.x - b.x, dy = a.y + b.y;
-                const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
-                v[j] = C{sx + wdx, sy + wdy};
-                if (!(j == 0 && t == 0)) {                          // Z[L] is no bin
-                    par_x[T * (15 - j) * CW] = sx - wdx;
-                    par_y[T * (15 - j) * CW] = wdy - sy;
-                }
-            }
-            lds_barrier();
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[16 + j] = C{own_x[T * j * CW], own_y[T * j * CW]};
-        }
-        if constexpr (MODE == DSC_MODE_C2R_PACKED && !PAIR_ONCE && T != 1 && !PRE_ONCE) {
-            // Z[k] = (a + conj b)/2 + wq (a - conj b), a = Y[k], b = Y[L-k], wq = (i/2) conj(W_2L^k), k = T j1 + t (dsc_fft.h:194-228):
-            // every thread for its own 32 bins, b through the staging plane one component at a time
-            const int tid = tid_now(), c = tid % CW, t = tid / CW;
-            R *stage = plane + c;
-            const C wbase = tw_real[t];
-            C yl = request_mid(tile);                               // bin L (thread 0), requested here as the round-2 form did
-            if (t == 0) { v[0].y = (R) 0; yl.y = (R) 0; }           // bins 0 and L: real parts only (dsc_fft.h:227-228)
-            R dx[32];
-            R *up = stage + t * CW;
-            const R *dn = stage + ((L - 31 * T) - t) * CW;
-#pragma unroll
-            for (int j1 = 0; j1 < 32; ++j1) up[T * j1 * CW] = v[j1].x;
-            if (t == 0) stage[L * CW] = yl.x;
-            lds_barrier();
-#pragma unroll
-            for (int j1 = 0; j1 < 32; ++j1) {
-                const R bx = dn[T * (31 - j1) * CW];
-                dx[j1] = v[j1].x - bx;
-                v[j1].x = v[j1].x + bx;
-            }
-            lds_barrier();
-#pragma unroll
-            for (int j1 = 0; j1 < 32; ++j1) up[T * j1 * CW] = v[j1].y;
-            if (t == 0) stage[L * CW] = yl.y;
-            lds_barrier();
-#pragma unroll
-            for (int j1 = 0; j1 < 32; ++j1) {
-                const R by = dn[T * (31 - j1) * CW];
-                const C w = cmul(wbase, C{(R) root64_re(j1), (R) root64_im(j1)});      // W_2L^{t + T j1} = W_2L^t W_64^{j1}
-                const R wqx = (R) 0.5 * w.y, wqy = (R) 0.5 * w.x;
-                const R sy = v[j1].y - by, dy = v[j1].y + by;
-                const R zx = (R) 0.5 * v[j1].x + (dx[j1] * wqx - dy * wqy);
-                const R zy = (R) 0.5 * sy + (dx[j1] * wqy + dy * wqx);
-                v[j1] = C{zx, zy};
+        for (int j = 0; j < 16; ++j) {
+            const C a = v[j];
+            C b = C{par_x[T * (15 - j) * CW], par_y[T * (15 - j) * CW]};
+            if (j == 0 && t == 0) b = yl;
+            const C w = cmul(wbase, C{(R) root64_re(j), (R) root64_im(j)});        // W_2L^{t + T j} = W_2L^t W_64^j
+            const R wqx = (R) 0.5 * w.y, wqy = (R) 0.5 * w.x;
+            const R sx = (R) 0.5 * (a.x + b.x), sy = (R) 0.5 * (a.y - b.y), dx = a.x - b.x, dy = a.y + b.y;
+            const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
+            v[j] = C{sx + wdx, sy + wdy};
+            if (!(j == 0 && t == 0)) {                          // Z[L] is no bin
+                par_x[T * (15 - j) * CW] = sx - wdx;
+                par_y[T * (15 - j) * CW] = wdy - sy;
             }
         }
-        if constexpr (MODE == DSC_MODE_C2R_PACKED && PAIR_ONCE) {
-            const int tid = tid_now(), c = tid % CW, t = tid / CW;
-            R *stage = plane + c;                                   // stage[k * CW] = component of bin k of this column
-            // pair (k, L - k), k = T j + t, j < 16: a = Y[k] = v[j], b = Y[L - k] = v[16 + j];  s = a + conj b, d = a - conj b,
-            // wq = (i/2) conj(W_2L^k):  Z[k] = s/2 + wq d (kept),  Z[L - k] = conj(s/2 - wq d) (handed to its owner)   (dsc_fft.h:194-228)
-            const C wbase = wpre;
-            if (t == 0) { v[0].y = (R) 0; v[16].y = (R) 0; }        // bins 0 and L: real parts only (dsc_fft.h:227-228)
+        lds_barrier();
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const C w = cmul(wbase, C{(R) root64_re(j), (R) root64_im(j)});        // W_2L^{t + T j} = W_2L^t W_64^j
-                const R wqx = (R) 0.5 * w.y, wqy = (R) 0.5 * w.x;
-                const C a = v[j], b = v[16 + j];
-                const R sx = (R) 0.5 * (a.x + b.x), sy = (R) 0.5 * (a.y - b.y), dx = a.x - b.x, dy = a.y + b.y;
-                const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
-                v[j] = C{sx + wdx, sy + wdy};
-                v[16 + j] = C{sx - wdx, wdy - sy};
-            }
-            // Z[L - k] goes to staging index L - k; everybody then reads its own upper half k' = T j' + t, j' = 16 .. 31.  Thread 0
-            // pairs with itself (its Z[L - T j] are its own rows 32 - j) and supplies Z[L/2] = conj Y[L/2]; its write at index L is never read.
-            R *up = stage + ((L - 15 * T) - t) * CW;                // index L - T j - t = (L - 15 T - t) + T (15 - j)
-            const R *dn = stage + (16 * T + t) * CW;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) up[T * (15 - j) * CW] = v[16 + j].x;
-            if (t == 0) stage[(L / 2) * CW] = ymid.x;
-            lds_barrier();
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[16 + j].x = dn[T * j * CW];
-            lds_barrier();
-#pragma unroll
-            for (int j = 0; j < 16; ++j) up[T * (15 - j) * CW] = v[16 + j].y;
-            if (t == 0) stage[(L / 2) * CW] = -ymid.y;
-            lds_barrier();
-#pragma unroll
-            for (int j = 0; j < 16; ++j) v[16 + j].y = dn[T * j * CW];
-        }
-        if constexpr (PIPE) lds_barrier();      // staging reads (this tile's pre-pass, the previous tile's post-pass) done before the plane is reused
-        else __syncthreads();                   // ... and the twiddle table visible
+        for (int j = 0; j < 16; ++j) v[16 + j] = C{own_x[T * j * CW], own_y[T * j * CW]};
+    }
+    __syncthreads();                                                // staging reads done before the plane is reused, the twiddle table visible
 
-        {
-            const int tid = tid_now();
-            cols_passes<R, B, TWO, CW, INV>(v, plane, wtab, tw_full, tid / CW, tid % CW);
-        }
-        const int tid = tid_now(), c = tid % CW, t = tid / CW;
-        const int col = col_of(tile, c);
-        const bool live = col < inner;
-        R *stage = plane + c;                                       // stage[k * CW] = component of bin k of this column
+    {
+        const int tid = (int) threadIdx.x;
+        cols_passes<R, B, TWO, CW, INV>(v, plane, wtab, tw_full, tid / CW, tid % CW);
+    }
+    const int tid = (int) threadIdx.x, c = tid % CW, t = tid / CW;
+    const int col = col_of(c);
+    const bool live = col < inner;
+    R *stage = plane + c;                                       // stage[k * CW] = component of bin k of this column
 
-        if constexpr (MODE == DSC_MODE_C2C || MODE == DSC_MODE_R2C_CAST) {
-            const int voff = live ? (t * rm.out_pitch + col) * CB : kOut;
-            const int step = rm.out_pitch * CB;
-            if (rm.tw4 != nullptr) {                                // four-step, pass 1: times W_n^{j1 k}, k the bin, j1 = col / tw4_div
-                const C *tw4 = (const C *) rm.tw4;
-                const int j1 = col / rm.tw4_div;
+    if constexpr (MODE == DSC_MODE_C2C || MODE == DSC_MODE_R2C_CAST) {
+        const int voff = live ? (t * rm.out_pitch + col) * CB : kOut;
+        const int step = rm.out_pitch * CB;
+        if (rm.tw4 != nullptr) {                                // four-step, pass 1: times W_n^{j1 k}, k the bin, j1 = col / tw4_div
+            const C *tw4 = (const C *) rm.tw4;
+            const int j1 = col / rm.tw4_div;
 #pragma unroll
-                for (int q = 0; q < 32; ++q) {
-                    const int k = t + T * (q / B) + COLS * brev(q % B, LOGB);
-                    const C w = tw4[live ? j1 * k : 0];
-                    v[q] = INV ? cmulc(v[q], w) : cmul(v[q], w);
-                }
-            }
-            auto put = [&](int q) {                                 // q = i B + p
-                const C r = v[q];
-                buf_store<kStream>(C{r.x * scale, r.y * scale}, rout, voff, (T * (q / B) + COLS * brev(q % B, LOGB)) * step);
-            };
-            if constexpr (PIPE) {
-                // (the scheduling fences keep hipcc from hoisting all 32 loads in front of the stores: v[] would still be live)
-                __builtin_amdgcn_sched_barrier(0);
-                C nx[16];
-                request(nx, i0{}, i16{}, next);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) put(q);
-                __builtin_amdgcn_sched_barrier(0);
-                C ny[16];
-                request(ny, i16{}, i16{}, next);                    // into the registers the first sixteen stores have read
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 16; q < 32; ++q) put(q);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) { v[j] = nx[j]; v[16 + j] = ny[j]; }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 32; ++q) put(q);
-            }
-        } else if constexpr (MODE == DSC_MODE_C2R_PACKED) {         // sample pair (2k, 2k + 1) = (re, im) of z[k]: two rows of the output axis
-            const int voff = live ? (2 * t * inner + col) * RB : kOut;
-            const int row_b = inner * RB;
-            auto put = [&](int q) {
-                const C r = v[q];
-                const int soff = 2 * (T * (q / B) + COLS * brev(q % B, LOGB)) * row_b;
-                store_real(r.x * scale, rout, voff, soff);
-                store_real(r.y * scale, rout, voff, soff + row_b);
-            };
-            if constexpr (PIPE) {
-                __builtin_amdgcn_sched_barrier(0);
-                C nx[16];
-                request(nx, i0{}, i16{}, next);
-                ymid = request_mid(next);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 0; q < 16; ++q) put(q);
-                __builtin_amdgcn_sched_barrier(0);
-                C ny[16];
-                request(ny, i16{}, i16{}, next);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int q = 16; q < 32; ++q) put(q);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 16; ++j) { v[j] = nx[j]; v[16 + j] = ny[j]; }
-            } else {
-#pragma unroll
-                for (int q = 0; q < 32; ++q) put(q);
-            }
-        } else if constexpr (POST_ONCE) {
-            // packed-real post-pass (dsc_fft.h:199-225): only the upper halves travel (see above), one barrier
-            const C wbase = tw_real[t];
-            auto reg_of = [](int m) constexpr { return (m % CPT) * B + brev(m / CPT, LOGB); };      // register that holds bin t + T m
-            R *own_x = stage + t * CW, *own_y = own_x + (L / 2) * CW;
-            const R *par_x = stage + ((L / 2 - 15 * T) - t) * CW, *par_y = par_x + (L / 2) * CW;
-#pragma unroll
-            for (int m = 16; m < 32; ++m) { own_x[T * (m - 16) * CW] = v[reg_of(m)].x; own_y[T * (m - 16) * CW] = v[reg_of(m)].y; }
-            const C zmid = v[reg_of(16)];                           // thread 0: bin L/2, which pairs with itself
-            lds_barrier();
-            const int step = inner * CB;
-            const int voff_k = live ? (t * inner + col) * CB : kOut;
-            const int voff_m = live ? (((L - 15 * T) - t) * inner + col) * CB : kOut;
-#pragma unroll
-            for (int m = 0; m < 16; ++m) {
-                const C a = v[reg_of(m)];
-                C b = C{par_x[T * (15 - m) * CW], par_y[T * (15 - m) * CW]};
-                if (m == 0 && t == 0) b = a;                        // Z[L] := Z[0]
-                const C w = cmul(wbase, C{(R) root64_re(m), (R) root64_im(m)});        // W_2L^{t + T m} = W_2L^t W_64^m
-                const R wqx = (R) 0.5 * w.y, wqy = (R) -0.5 * w.x;
-                const R sx = a.x + b.x, sy = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
-                const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
-                C xk = C{(R) 0.5 * sx + wdx, (R) 0.5 * sy + wdy};
-                C xm = C{(R) 0.5 * sx - wdx, wdy - (R) 0.5 * sy};
-                if (m == 0 && t == 0) { xk.y = (R) 0; xm.y = (R) 0; }           // dsc_fft.h:221-225 stores exact zeros
-                buf_store<kStream>(C{xk.x * scale, xk.y * scale}, rout, voff_k, T * m * step);
-                buf_store<kStream>(C{xm.x * scale, xm.y * scale}, rout, voff_m, T * (15 - m) * step);
-            }
-            if (t == 0) buf_store<kStream>(C{zmid.x * scale, -zmid.y * scale}, rout, voff_k, (L / 2) * step);     // k = L/2: a = b, W_2L^{L/2} = -i
-        } else {
-            // packed-real post-pass (dsc_fft.h:199-225), one thread per PAIR (k, L-k), k = t + T i < L/2, plus k = L/2 (thread 0)
-            const C wbase = tw_real[t];
-            R ax[16], bx[16], amx = (R) 0;
-            R *up = stage + t * CW;
-            const R *dn = stage + ((L - 15 * T) - t) * CW;
-#pragma unroll
-            for (int i = 0; i < CPT; ++i)
-#pragma unroll
-                for (int p = 0; p < B; ++p) up[(T * i + COLS * brev(p, LOGB)) * CW] = v[i * B + p].x;
-            if (t == 0) stage[L * CW] = v[0].x;                                   // Z[L] := Z[0]
-            lds_barrier();
-#pragma unroll
-            for (int i = 0; i < 16; ++i) { ax[i] = up[T * i * CW]; bx[i] = dn[T * (15 - i) * CW]; }
-            if (t == 0) amx = stage[(L / 2) * CW];
-            lds_barrier();
-#pragma unroll
-            for (int i = 0; i < CPT; ++i)
-#pragma unroll
-                for (int p = 0; p < B; ++p) up[(T * i + COLS * brev(p, LOGB)) * CW] = v[i * B + p].y;
-            if (t == 0) stage[L * CW] = v[0].y;
-            if constexpr (PIPE) {                                   // v is in the staging plane: its registers take the next tile
-                __builtin_amdgcn_sched_barrier(0);
-                request(v, i0{}, i32{}, next);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            lds_barrier();
-            const int step = inner * CB;
-            const int voff_k = live ? (t * inner + col) * CB : kOut;
-            const int voff_m = live ? (((L - 15 * T) - t) * inner + col) * CB : kOut;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const R ay = up[T * i * CW], by = dn[T * (15 - i) * CW];
-                const C w = cmul(wbase, C{(R) root64_re(i), (R) root64_im(i)});        // W_2L^{t + T i} = W_2L^t W_64^i
-                const R wqx = (R) 0.5 * w.y, wqy = (R) -0.5 * w.x;
-                const R sx = ax[i] + bx[i], sy = ay - by, dx = ax[i] - bx[i], dy = ay + by;
-                const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
-                C xk = C{(R) 0.5 * sx + wdx, (R) 0.5 * sy + wdy};
-                C xm = C{(R) 0.5 * sx - wdx, wdy - (R) 0.5 * sy};
-                if (i == 0 && t == 0) { xk.y = (R) 0; xm.y = (R) 0; }           // dsc_fft.h:221-225 stores exact zeros
-                buf_store<kStream>(C{xk.x * scale, xk.y * scale}, rout, voff_k, T * i * step);
-                buf_store<kStream>(C{xm.x * scale, xm.y * scale}, rout, voff_m, T * (15 - i) * step);
-            }
-            if (t == 0) {                                                     // k = L/2: a = b, W_2L^{L/2} = -i
-                const R ay = stage[(L / 2) * CW];
-                buf_store<kStream>(C{amx * scale, -ay * scale}, rout, voff_k, (L / 2) * step);
+            for (int q = 0; q < 32; ++q) {
+                const int k = t + T * (q / B) + COLS * brev(q % B, LOGB);
+                const C w = tw4[live ? j1 * k : 0];
+                v[q] = INV ? cmulc(v[q], w) : cmul(v[q], w);
             }
         }
-    } while (PIPE && (tile += (int) gridDim.x) < n_tiles);
+        auto put = [&](int q) {                                     // q = i B + p
+            const C r = v[q];
+            buf_store<kStream>(C{r.x * scale, r.y * scale}, rout, voff, (T * (q / B) + COLS * brev(q % B, LOGB)) * step);
+        };
+#pragma unroll
+        for (int q = 0; q < 32; ++q) put(q);
+    } else if constexpr (MODE == DSC_MODE_C2R_PACKED) {         // sample pair (2k, 2k + 1) = (re, im) of z[k]: two rows of the output axis
+        const int voff = live ? (2 * t * inner + col) * RB : kOut;
+        const int row_b = inner * RB;
+        auto put = [&](int q) {
+            const C r = v[q];
+            const int soff = 2 * (T * (q / B) + COLS * brev(q % B, LOGB)) * row_b;
+            store_real(r.x * scale, rout, voff, soff);
+            store_real(r.y * scale, rout, voff, soff + row_b);
+        };
+#pragma unroll
+        for (int q = 0; q < 32; ++q) put(q);
+    } else if constexpr (T >= 2) {
+        // packed-real post-pass (dsc_fft.h:199-225): only the upper halves travel (see above), one barrier
+        const C wbase = tw_real[t];
+        auto reg_of = [](int m) constexpr { return (m % CPT) * B + brev(m / CPT, LOGB); };      // register that holds bin t + T m
+        R *own_x = stage + t * CW, *own_y = own_x + (L / 2) * CW;
+        const R *par_x = stage + ((L / 2 - 15 * T) - t) * CW, *par_y = par_x + (L / 2) * CW;
+#pragma unroll
+        for (int m = 16; m < 32; ++m) { own_x[T * (m - 16) * CW] = v[reg_of(m)].x; own_y[T * (m - 16) * CW] = v[reg_of(m)].y; }
+        const C zmid = v[reg_of(16)];                           // thread 0: bin L/2, which pairs with itself
+        lds_barrier();
+        const int step = inner * CB;
+        const int voff_k = live ? (t * inner + col) * CB : kOut;
+        const int voff_m = live ? (((L - 15 * T) - t) * inner + col) * CB : kOut;
+#pragma unroll
+        for (int m = 0; m < 16; ++m) {
+            const C a = v[reg_of(m)];
+            C b = C{par_x[T * (15 - m) * CW], par_y[T * (15 - m) * CW]};
+            if (m == 0 && t == 0) b = a;                        // Z[L] := Z[0]
+            const C w = cmul(wbase, C{(R) root64_re(m), (R) root64_im(m)});        // W_2L^{t + T m} = W_2L^t W_64^m
+            const R wqx = (R) 0.5 * w.y, wqy = (R) -0.5 * w.x;
+            const R sx = a.x + b.x, sy = a.y - b.y, dx = a.x - b.x, dy = a.y + b.y;
+            const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
+            C xk = C{(R) 0.5 * sx + wdx, (R) 0.5 * sy + wdy};
+            C xm = C{(R) 0.5 * sx - wdx, wdy - (R) 0.5 * sy};
+            if (m == 0 && t == 0) { xk.y = (R) 0; xm.y = (R) 0; }           // dsc_fft.h:221-225 stores exact zeros
+            buf_store<kStream>(C{xk.x * scale, xk.y * scale}, rout, voff_k, T * m * step);
+            buf_store<kStream>(C{xm.x * scale, xm.y * scale}, rout, voff_m, T * (15 - m) * step);
+        }
+        if (t == 0) buf_store<kStream>(C{zmid.x * scale, -zmid.y * scale}, rout, voff_k, (L / 2) * step);     // k = L/2: a = b, W_2L^{L/2} = -i
+    } else {
+        // packed-real post-pass (dsc_fft.h:199-225) of 32-point lines, one thread per PAIR (k, L-k), k = t + T i < L/2, plus k = L/2
+        // (thread 0): both halves through the staging plane, one component at a time
+        const C wbase = tw_real[t];
+        R ax[16], bx[16], amx = (R) 0;
+        R *up = stage + t * CW;
+        const R *dn = stage + ((L - 15 * T) - t) * CW;
+#pragma unroll
+        for (int i = 0; i < CPT; ++i)
+#pragma unroll
+            for (int p = 0; p < B; ++p) up[(T * i + COLS * brev(p, LOGB)) * CW] = v[i * B + p].x;
+        if (t == 0) stage[L * CW] = v[0].x;                                   // Z[L] := Z[0]
+        lds_barrier();
+#pragma unroll
+        for (int i = 0; i < 16; ++i) { ax[i] = up[T * i * CW]; bx[i] = dn[T * (15 - i) * CW]; }
+        if (t == 0) amx = stage[(L / 2) * CW];
+        lds_barrier();
+#pragma unroll
+        for (int i = 0; i < CPT; ++i)
+#pragma unroll
+            for (int p = 0; p < B; ++p) up[(T * i + COLS * brev(p, LOGB)) * CW] = v[i * B + p].y;
+        if (t == 0) stage[L * CW] = v[0].y;
+        lds_barrier();
+        const int step = inner * CB;
+        const int voff_k = live ? (t * inner + col) * CB : kOut;
+        const int voff_m = live ? (((L - 15 * T) - t) * inner + col) * CB : kOut;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const R ay = up[T * i * CW], by = dn[T * (15 - i) * CW];
+            const C w = cmul(wbase, C{(R) root64_re(i), (R) root64_im(i)});        // W_2L^{t + T i} = W_2L^t W_64^i
+            const R wqx = (R) 0.5 * w.y, wqy = (R) -0.5 * w.x;
+            const R sx = ax[i] + bx[i], sy = ay - by, dx = ax[i] - bx[i], dy = ay + by;
+            const R wdx = dx * wqx - dy * wqy, wdy = dx * wqy + dy * wqx;
+            C xk = C{(R) 0.5 * sx + wdx, (R) 0.5 * sy + wdy};
+            C xm = C{(R) 0.5 * sx - wdx, wdy - (R) 0.5 * sy};
+            if (i == 0 && t == 0) { xk.y = (R) 0; xm.y = (R) 0; }           // dsc_fft.h:221-225 stores exact zeros
+            buf_store<kStream>(C{xk.x * scale, xk.y * scale}, rout, voff_k, T * i * step);
+            buf_store<kStream>(C{xm.x * scale, xm.y * scale}, rout, voff_m, T * (15 - i) * step);
+        }
+        if (t == 0) {                                                     // k = L/2: a = b, W_2L^{L/2} = -i
+            const R ay = stage[(L / 2) * CW];
+            buf_store<kStream>(C{amx * scale, -ay * scale}, rout, voff_k, (L / 2) * step);
+        }
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -806,7 +653,6 @@ static void launch_cols_len(const void *in, void *out, long long slices, int inn
             const int tiles = (inner + CW - 1) / CW;
             const long long n_tiles = slices * tiles;
             long long grid = n_tiles;
-            if (cfg::PIPE && !TWO) grid = std::min<long long>(grid, dsc_cu_count());      // persistent: one workgroup per CU walks the tiles
             dsc_launch_dyn_lds<fft_cols_kernel<R, B, TWO, CW, decltype(m)::value, decltype(inv)::value>>(
                 (unsigned) grid, cfg::NT, cols_lds_bytes<R, B, TWO, CW>(), stream, in, out, inner, tiles, (int) n_tiles, in_axis, in_len, out_axis,
                 (const cpx<R> *) tw_full, (const cpx<R> *) tw_real, (R) scale, rm);

@@ -41,42 +41,7 @@ constexpr int two_pass_stride(int B) {
     return base;
 }
 
-// V: 0 = the transforms (fft_mid_kernel), 1 = the fused filter (fft_mid_filter_kernel) — the two want different group sizes at some lengths
-template<typename R, int B, bool TWO, int V = 0> struct mid_cfg {
-    static constexpr bool DP = sizeof(R) == 8;
-    static constexpr int T = TWO ? B : 32 * B;       // threads per line
-    static constexpr int L = 32 * T;                 // complex length
-    static constexpr int COLS = TWO ? 32 : 1024;     // columns entering the last pass (DFT_B down each)
-    // threads per workgroup.  f32: a thread needs ~100 VGPRs and 132-264 B of LDS, so two 512-thread groups (or three
-    // of 256) share a CU and overlap each other's load / compute / store phases.  f64: twice the registers (one
-    // 512-thread group or several smaller ones per CU) and twice the LDS, which decides the group size.
-#ifdef DSC_MID_PADDED_SHORT
-    static constexpr bool PACKED = false;
-#else
-    // Three-pass lines of 2048 points (B = 2): the last exchange keeps its 2-value rows UNPADDED and reads a row as one 8- /
-    // 16-byte access (conflict free, like the stride-1 writes) — the padded pitch 3 cost 50 % more LDS and left two 256-thread
-    // groups (two waves per SIMD) on a CU in f32; unpadded, two 512-thread groups fit (four per SIMD): irfft N = 4096 64.6 ->
-    // 71 %, fft 68 -> 73 %, fused filter 31 -> 38.6 %.  (f32 B = 4 measured too: 1 % slower, stays padded.)  f64 B = 4 (4096-point
-    // lines, one 128-thread group per line): 4-value rows unpadded, read as two 16-byte accesses (2-way conflicts) — three groups
-    // per CU instead of two: rfft N = 8192 62.5 -> 69.3 %, irfft 60 -> 71.2 %, fft c64 71 -> 78.7 %.
-#ifdef DSC_MID_NO_F64_B4
-    static constexpr bool PACKED = !TWO && B == 2;
-#else
-    static constexpr bool PACKED = !TWO && (B == 2 || (DP && B == 4));
-#endif
-#endif
-#ifdef DSC_MID_NO_HALF_TABLE   // (A/B switch)
-    static constexpr bool HALF = false;
-#else
-    // f64 lines of 8192 points (B = 8): two lines per 512-thread group filled the whole LDS (144 KiB plane + 16 KiB table), i.e. ONE
-    // group per CU with nothing to overlap its load / compute / store phases with.  One line per 256-thread group and HALF the
-    // W_1024 table (W^(m + 512) = -W^m) is exactly 80 KiB: two independent groups per CU.
-    static constexpr bool HALF = DP && !TWO && B == 8;
-#endif
-    // f32 group sizes, round 3 (tools/build_mid_variant.sh, one box, gpurun_out/r3e/mid_nt.txt): 2048-point lines (B = 2) in groups of
-    // 256 threads instead of 512 — four independent groups per CU instead of two: fused filter N = 4096 0.701 -> 0.646 ms (38.3 -> 41.6 %),
-    // irfft 71.2 -> 73.2 %, rfft 68.7 -> 69.8 % (128: no better); 8192-point lines (B = 8) in groups of 256 for the FILTER only (0.772 ->
-    // 0.695 ms, 34.8 -> 38.6 %; the transforms lose 2 % with it); 4096-point lines (B = 4) stay at 256 (128: filter 40.4 -> 37.9 %; 512: everything 25 - 35 % slower).
+// Group sizes (threads per workgroup) of mid_cfg below: A/B knobs, overridable per build (tools/build_mid_variant.sh); see its NT.
 #ifndef DSC_MID_NT_F32_B2
 #define DSC_MID_NT_F32_B2 256
 #endif
@@ -95,6 +60,31 @@ template<typename R, int B, bool TWO, int V = 0> struct mid_cfg {
 #ifndef DSC_MID_NT_F32_B8_FILTER
 #define DSC_MID_NT_F32_B8_FILTER 256
 #endif
+
+// V: 0 = the transforms (fft_mid_kernel), 1 = the fused filter (fft_mid_filter_kernel) — the two want different group sizes at some lengths
+template<typename R, int B, bool TWO, int V = 0> struct mid_cfg {
+    static constexpr bool DP = sizeof(R) == 8;
+    static constexpr int T = TWO ? B : 32 * B;       // threads per line
+    static constexpr int L = 32 * T;                 // complex length
+    static constexpr int COLS = TWO ? 32 : 1024;     // columns entering the last pass (DFT_B down each)
+    // threads per workgroup.  f32: a thread needs ~100 VGPRs and 132-264 B of LDS, so two 512-thread groups (or three
+    // of 256) share a CU and overlap each other's load / compute / store phases.  f64: twice the registers (one
+    // 512-thread group or several smaller ones per CU) and twice the LDS, which decides the group size.
+    // Three-pass lines of 2048 points (B = 2): the last exchange keeps its 2-value rows UNPADDED and reads a row as one 8- /
+    // 16-byte access (conflict free, like the stride-1 writes) — the padded pitch 3 cost 50 % more LDS and left two 256-thread
+    // groups (two waves per SIMD) on a CU in f32; unpadded, two 512-thread groups fit (four per SIMD): irfft N = 4096 64.6 ->
+    // 71 %, fft 68 -> 73 %, fused filter 31 -> 38.6 %.  (f32 B = 4 measured too: 1 % slower, stays padded.)  f64 B = 4 (4096-point
+    // lines, one 128-thread group per line): 4-value rows unpadded, read as two 16-byte accesses (2-way conflicts) — three groups
+    // per CU instead of two: rfft N = 8192 62.5 -> 69.3 %, irfft 60 -> 71.2 %, fft c64 71 -> 78.7 %.
+    static constexpr bool PACKED = !TWO && (B == 2 || (DP && B == 4));
+    // f64 lines of 8192 points (B = 8): two lines per 512-thread group filled the whole LDS (144 KiB plane + 16 KiB table), i.e. ONE
+    // group per CU with nothing to overlap its load / compute / store phases with.  One line per 256-thread group and HALF the
+    // W_1024 table (W^(m + 512) = -W^m) is exactly 80 KiB: two independent groups per CU.
+    static constexpr bool HALF = DP && !TWO && B == 8;
+    // f32 group sizes, round 3 (tools/build_mid_variant.sh, one box, gpurun_out/r3e/mid_nt.txt): 2048-point lines (B = 2) in groups of
+    // 256 threads instead of 512 — four independent groups per CU instead of two: fused filter N = 4096 0.701 -> 0.646 ms (38.3 -> 41.6 %),
+    // irfft 71.2 -> 73.2 %, rfft 68.7 -> 69.8 % (128: no better); 8192-point lines (B = 8) in groups of 256 for the FILTER only (0.772 ->
+    // 0.695 ms, 34.8 -> 38.6 %; the transforms lose 2 % with it); 4096-point lines (B = 4) stay at 256 (128: filter 40.4 -> 37.9 %; 512: everything 25 - 35 % slower).
     static constexpr int NT = DP ? (TWO ? (B >= 32 ? 128 : DSC_MID_NT_F64_TWO16) : HALF ? 256 : (B >= 8 ? 512 : 128))
                                  : (TWO ? DSC_MID_NT_F32_TWO : B >= 32 ? 1024 : B == 16 ? 512 : B == 8 ? (V == 1 ? DSC_MID_NT_F32_B8_FILTER : DSC_MID_NT_F32_B8)
                                                                                   : B == 4 ? DSC_MID_NT_F32_B4 : (PACKED ? DSC_MID_NT_F32_B2 : 256));
@@ -102,11 +92,29 @@ template<typename R, int B, bool TWO, int V = 0> struct mid_cfg {
     // f64 lines of 16384 points: ONE 512-thread group per CU (131 KiB plane) — nothing to overlap its load / compute / store phases
     // with.  PIPE: the group is persistent (lines blockIdx.x, + gridDim.x, ...) and requests its next line into the registers the stores
     // (complex, inverse real) or the last staging write (forward real) have just freed, the way the 65536-point kernels do.
-#ifdef DSC_MID_NO_PIPE
-    static constexpr bool PIPE = false;
-#else
     static constexpr bool PIPE = DP && !TWO && B == 16 && V == 0;
-#endif
+    // ... its real transforms: streaming loads + cached stores measured best (tools/r03_call_p.sh: rfft 55.6 -> 56.2 %, irfft 50.9 ->
+    // 52.4 %; streaming stores: rfft 52 %)
+    static constexpr int PIPE_REAL_LOAD = kStream, PIPE_REAL_STORE = kCached;
+    // The packed-real passes that move only the upper halves through the staging plane, every pair computed once (fft_mid_kernel, "who
+    // owns which bin"), against the two-exchange forms.  Both forms are in use:
+    // PRE_ONCE, the inverse pre-pass.  Measured against the two-exchange form (tools/r03_call_s.sh): f32 lines of 16384 points 67.5 ->
+    // 70.4 % (it replaced a form that loaded the partners from memory, 4 spilled registers), the persistent f64 lines of 16384 points
+    // 52.3 -> 55.0 % (43 spilled registers -> 0), everything else within +- 0.8 points; the two f64 forms that measured 0.7 - 1 point
+    // lower with it (lines of 1024 and 2048 points) keep the two-exchange form.
+    static constexpr bool PRE_ONCE = !(DP && ((TWO && B == 32) || (!TWO && B == 2)));
+    // POST_ONCE, the forward post-pass.  Measured (tools/r03_call_o.sh): f32 + 0 - 1.7 points at every three-pass length; f64 lines of
+    // 2048 - 8192 points lose 1 - 2 points with it (they keep the two-exchange form), the persistent f64 lines of 16384 points need its
+    // registers (49 -> 55 %).  Two-pass lines (the same ownership: COLS = T CPT there too): f32 + 0.3 - 0.6 points, f64 no gain
+    // (tools/r03_call_r.sh).
+    static constexpr bool POST_ONCE = TWO ? (!DP && B > 1) : (!DP || B == 16);
+    // FILTER_ONCE, the fused filter's pair step (post-pass, times H, pre-pass) in the same ownership.  Two-pass lines, measured
+    // (tools/r03_call_r.sh): f32 N = 512 / 1024 / 2048: 48.6 -> 50.2, 50.2 -> 54.1, 44.9 -> 49.3 %; f64 N = 512 57.7 -> 60.1 %, but
+    // N = 1024 and 2048 LOSE with it (59.7 -> 49.1, 56.8 -> 50.6 %: the second 32-value array costs their occupancy).
+    static constexpr bool FILTER_ONCE = !TWO || !DP || B == 8;
+    // KEEP_X, hilbert / envelope: keep the row's 32 sample pairs in registers from the load to the store instead of loading them a
+    // second time (fft_mid_filter_kernel, the HILBERT store).  ENVELOPE: the real store, against the complex one.
+    template<bool ENVELOPE> static constexpr bool KEEP_X = !DP ? (!TWO && B >= 8) : ((TWO && B == 32) || (!TWO && (B <= 4 || (B == 8 && !ENVELOPE))));
     static constexpr int WAVES_PER_EU = DP ? 2 : (TWO ? 2 : (B >= 8 || PACKED) ? 4 : 2);   // f32: <= 128 VGPRs where two 512-thread groups share a CU
     static constexpr int P1 = 33;                    // exchange-1 row pitch (values): odd
     static constexpr int P2 = PACKED ? B : B + 1;    // last-exchange row pitch
@@ -331,16 +339,8 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
     // ones from streaming their (aligned) stores at L >= 2048; everything that touches rows of L + 1 bins, and the
     // forward real transform as a whole, is faster cached (see fft_regs_common.h)
     constexpr bool kComplex = MODE == DSC_MODE_C2C || MODE == DSC_MODE_R2C_CAST;
-    // the persistent f64 lines (PIPE): streaming loads + cached stores measured best for the real transforms (tools/r03_call_p.sh:
-    // rfft 55.6 -> 56.2 %, irfft 50.9 -> 52.4 %; streaming stores: rfft 52 %)
-#ifndef DSC_MID_PIPE_REAL_LOAD
-#define DSC_MID_PIPE_REAL_LOAD kStream
-#endif
-#ifndef DSC_MID_PIPE_REAL_STORE
-#define DSC_MID_PIPE_REAL_STORE kCached
-#endif
-    constexpr int LOADP = kComplex ? kStream : cfg::PIPE ? DSC_MID_PIPE_REAL_LOAD : kCached;
-    constexpr int STOREP = kComplex || (MODE == DSC_MODE_C2R_PACKED && !TWO) ? kStream : (cfg::PIPE && MODE == DSC_MODE_R2C_PACKED) ? DSC_MID_PIPE_REAL_STORE : kCached;
+    constexpr int LOADP = kComplex ? kStream : cfg::PIPE ? cfg::PIPE_REAL_LOAD : kCached;
+    constexpr int STOREP = kComplex || (MODE == DSC_MODE_C2R_PACKED && !TWO) ? kStream : (cfg::PIPE && MODE == DSC_MODE_R2C_PACKED) ? cfg::PIPE_REAL_STORE : kCached;
     const int pitch_b = PAD ? in_pitch_b : in_pitch * IB;
     auto in_rsrc = [&](long long first) {
         if constexpr (FRAMES) return __builtin_amdgcn_make_buffer_rsrc((void *) fr.x, 0, fr.x_bytes, 0x00020000);
@@ -384,23 +384,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO>::NT), (mid_cfg<R, B, TWO>::WAVE
             }
         }
     }
-#ifdef DSC_MID_OLD_PRE
-    constexpr bool PRE_ONCE = false;
-#else
-    // the inverse pre-pass that moves only the upper halves (see there).  Measured against the two-exchange form (tools/r03_call_s.sh):
-    // f32 lines of 16384 points 67.5 -> 70.4 % (it replaced a form that loaded the partners from memory, 4 spilled registers), the
-    // persistent f64 lines of 16384 points 52.3 -> 55.0 % (43 spilled registers -> 0), everything else within +- 0.8 points; the two
-    // f64 forms that measured 0.7 - 1 point lower with it (lines of 1024 and 2048 points) keep the two-exchange form.
-    constexpr bool PRE_ONCE = !(sizeof(R) == 8 && ((TWO && B == 32) || (!TWO && B == 2)));
-#endif
-#ifdef DSC_MID_OLD_POST
-    constexpr bool POST_ONCE = false;
-#else
-    // measured (tools/r03_call_o.sh): f32 + 0 - 1.7 points at every three-pass length; f64 lines of 2048 - 8192 points lose 1 - 2 points
-    // with it (they keep the two-exchange form), the persistent f64 lines of 16384 points need its registers (49 -> 55 %)
-    // two-pass lines (the same ownership: COLS = T CPT there too): f32 + 0.3 - 0.6 points, f64 no gain (tools/r03_call_r.sh)
-    constexpr bool POST_ONCE = TWO ? (sizeof(R) == 4 && B > 1) : (sizeof(R) == 4 || B == 16);
-#endif
+    constexpr bool PRE_ONCE = cfg::PRE_ONCE, POST_ONCE = cfg::POST_ONCE;       // which form of the real passes: see mid_cfg
     if constexpr (!FRAMES) {
 #pragma unroll
         for (int j1 = 0; j1 < 32; ++j1) v[j1] = load_elem(T * j1);                           // z[T j1 + t]
@@ -723,14 +707,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
     __syncthreads();
     mid_passes<R, B, TWO, false, 1>(v, plane, wtab, tw_full, g, t, tid);  // v[i B + p] = Z[(t + T i) + COLS brev(p)]
 
-#ifdef DSC_MID_OLD_FILTER_PAIRS
-    constexpr bool ONCE = false;
-#else
-    // two-pass lines, measured (tools/r03_call_r.sh): f32 N = 512 / 1024 / 2048: 48.6 -> 50.2, 50.2 -> 54.1, 44.9 -> 49.3 %; f64 N = 512
-    // 57.7 -> 60.1 %, but N = 1024 and 2048 LOSE with it (59.7 -> 49.1, 56.8 -> 50.6 %: the second 32-value array costs their occupancy)
-    constexpr bool ONCE = !TWO || sizeof(R) == 4 || B == 8;
-#endif
-    if constexpr (ONCE) {
+    if constexpr (cfg::FILTER_ONCE) {
         // ---- three-pass lines, round 3.  The column layout leaves thread t with the bins t + T m, m = 0 .. 31: its sixteen lower bins k
         // and sixteen upper ones; the partners L - k of its lower bins are upper bins of thread T - t.  Only the upper halves travel, both
         // components at once (slot of upper bin b: b - L/2; x plane [0, L/2), y plane [L/2, L)): write them, ONE barrier, then per pair
@@ -905,13 +882,7 @@ __global__ __launch_bounds__((mid_cfg<R, B, TWO, 1>::NT), (mid_cfg<R, B, TWO, 1>
         // -7 %): elsewhere it spills or costs a wave per SIMD (f32 lines of 2048 points: +26 %), and the load goes through an opaque
         // copy of the thread's offset, i.e. is made again.  It then misses the L2 (FETCH_SIZE x1.9 of the plain filter's,
         // profiles/hilbert_trace.md) and is served past it.  tools/bench_hilbert.py on both builds, DESIGN 4.8.
-#if defined(DSC_HILBERT_KEEP_X)         // (A/B switches)
-        constexpr bool KEEP_X = true;
-#elif defined(DSC_HILBERT_REREAD_X)
-        constexpr bool KEEP_X = false;
-#else
-        constexpr bool KEEP_X = sizeof(R) == 4 ? (!TWO && B >= 8) : ((TWO && B == 32) || (!TWO && (B <= 4 || (B == 8 && !ENVELOPE))));
-#endif
+        constexpr bool KEEP_X = cfg::template KEEP_X<ENVELOPE>;
         int vin2 = vin;
         if constexpr (!KEEP_X) asm volatile("" : "+v"(vin2));
         const int vout2 = ENVELOPE ? vout : 2 * vout;

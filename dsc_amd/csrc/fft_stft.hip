@@ -7,7 +7,7 @@
 //   istft_ola_kernel    overlap-add as a GATHER: one thread per output sample sums the frames that cover it, in increasing frame
 //                       order, each times w[j], and divides by the sum of w[j]^2 over the same frames.  Every sample is written
 //                       once, without atomics: the result does not depend on the schedule.
-#include "kernels.h"
+#include "dispatch.h"
 
 #include <hip/hip_runtime.h>
 
@@ -59,11 +59,6 @@ __global__ __launch_bounds__(kThreads) void istft_ola_kernel(const R *__restrict
     }
 }
 
-unsigned grid_for(long long total) {
-    const long long blocks = (total + kThreads - 1) / kThreads;
-    return (unsigned) (blocks < 65536 ? (blocks > 0 ? blocks : 1) : 65536);
-}
-
 }  // namespace
 
 void dsc_launch_stft_frames(const void *x, const void *w, void *frames, long long q0, long long n_lines, int n_fft, long long T, int n_frames,
@@ -72,12 +67,11 @@ void dsc_launch_stft_frames(const void *x, const void *w, void *frames, long lon
     if (total <= 0) return;
     int log2n = 0;
     while ((1 << log2n) < n_fft) ++log2n;
-    if (single_precision)
-        DSC_LAUNCH(stft_frames_kernel<float>, dim3(grid_for(total)), dim3(kThreads), 0, stream, (const float *) x, (const float *) w,
-                   (float *) frames, q0, total, log2n, T, n_frames, hop, pad, reflect);
-    else
-        DSC_LAUNCH(stft_frames_kernel<double>, dim3(grid_for(total)), dim3(kThreads), 0, stream, (const double *) x, (const double *) w,
-                   (double *) frames, q0, total, log2n, T, n_frames, hop, pad, reflect);
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        DSC_LAUNCH(stft_frames_kernel<R>, dim3(dsc_grid_for(total, kThreads)), dim3(kThreads), 0, stream, (const R *) x, (const R *) w, (R *) frames, q0,
+                   total, log2n, T, n_frames, hop, pad, reflect);
+    });
 }
 
 void dsc_launch_istft_ola(const void *frames, const void *w, void *y, long long r0, long long rows, int fa, int fpr, int n_fft, int hop,
@@ -87,10 +81,9 @@ void dsc_launch_istft_ola(const void *frames, const void *w, void *y, long long 
     const long long span = p1 - p0;
     if (rows <= 0 || span <= 0) return;
     const long long total = rows * span;
-    if (single_precision)
-        DSC_LAUNCH(istft_ola_kernel<float>, dim3(grid_for(total)), dim3(kThreads), 0, stream, (const float *) frames, (const float *) w, (float *) y,
-                   r0, rows, fa, fpr, n_fft, hop, n_frames, pad, p0, span, length);
-    else
-        DSC_LAUNCH(istft_ola_kernel<double>, dim3(grid_for(total)), dim3(kThreads), 0, stream, (const double *) frames, (const double *) w,
-                   (double *) y, r0, rows, fa, fpr, n_fft, hop, n_frames, pad, p0, span, length);
+    with_real(single_precision, [&](auto real) {
+        using R = decltype(real);
+        DSC_LAUNCH(istft_ola_kernel<R>, dim3(dsc_grid_for(total, kThreads)), dim3(kThreads), 0, stream, (const R *) frames, (const R *) w, (R *) y, r0, rows,
+                   fa, fpr, n_fft, hop, n_frames, pad, p0, span, length);
+    });
 }

@@ -10,7 +10,8 @@
           for each polyphase tile form.  DSC_NO_FUSED_L2=1: rows of 65536 and 131072 points reach the two-pass launcher.  Then the
           operators (stft, istft, convolve, correlate, hilbert, envelope, fft2, cumsum, unwrap, diff, resample_poly): one small call per
           route, the composed routes with their DSC_NO_..._FUSED switch set around the call, scan_rows / scan_tiles through
-          DSC_SCAN_ROUTE, and the chunked branches of stft, istft, convolve, correlate, hilbert and envelope at n = 1024 in a second
+          DSC_SCAN_ROUTE, hilbert / envelope also on f32 rows long enough to be filtered in f64 and from rows off the 16-byte alignment
+          (every instantiation of the composed route's store), and the chunked branches of stft, istft, convolve, correlate, hilbert and envelope at n = 1024 in a second
           context with 64 KiB of scratch, three chunks each.  Then the streaming files (elementwise, layout, reduce): one small call per
           branch of every launcher in them x the four dtypes — the five binary operators on every broadcast route and with operands of
           two dtypes, the unary functions, casts and arange at aligned, odd and 8-bytes-off-alignment counts, the four reductions on
@@ -101,6 +102,25 @@ def switch(name, value='1'):
         del os.environ[name]
 
 
+@contextlib.contextmanager
+def offset_ones(dsc, np, shape, dt):
+    """ones in a view 8 bytes off the 16-byte alignment of the packed kernels, as tests/test_gpu_math_ops.py::_Offset"""
+    import ctypes
+    from dsc_amd import _bindings as B
+    from dsc_amd.context import _get_ctx
+    from dsc_amd.dtype import NP_TO_DTYPE
+    x = np.ones(shape, dtype=dt)
+    raw = B.dsc_device_alloc(_get_ctx(), x.nbytes + 256)
+    view = dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), raw + 8, x.nbytes, x.ndim, (ctypes.c_int * x.ndim)(*shape), NP_TO_DTYPE[x.dtype].value))
+    B.dsc_copy_from_host(_get_ctx(), view._c_ptr, x.ctypes.data, x.nbytes)
+    try:
+        yield view
+    finally:
+        del view
+        dsc.synchronize()
+        B.dsc_device_free(_get_ctx(), raw)
+
+
 def operators(dsc, np, call):
     F32, F64 = np.float32, np.float64
     cpx = {F32: np.complex64, F64: np.complex128}
@@ -127,6 +147,14 @@ def operators(dsc, np, call):
         call('convolve', lambda x: dsc.convolve(x, ones(40000, dt), 'same'), (1, 50000), dt)
         call('hilbert', dsc.hilbert, (3, 64), dt)
         call('envelope', dsc.envelope, (2, 1 << 17), dt)                              # f32: widened rows
+        call('hilbert', dsc.hilbert, (2, 1 << 17), dt)                                #      ... and their complex store
+        # the composed route's store from rows whose base is not 16-byte aligned (sample by sample); f32 also at the widened length
+        for shape in ((3, 1024),) + (((2, 1 << 17),) if dt == F32 else ()):
+            with switch('DSC_NO_HILBERT_FUSED'), offset_ones(dsc, np, shape, dt) as x:
+                for name in ('hilbert', 'envelope'):
+                    y = getattr(dsc, name)(x)
+                    print('CALL', name, np.dtype(dt).name, shape, 'unaligned', dsc.last_fft_path(), flush=True)
+                    del y
         for fused in (True, False):
             with contextlib.nullcontext() if fused else switch('DSC_NO_FFT2_FUSED'):
                 call('fft2', dsc.fft2, (2, 32, 32), cpx[dt])
@@ -176,19 +204,8 @@ def streaming(dsc, np):
         print('CALL', what, np.dtype(dt).name, shape, *note, flush=True)
         del x, y
 
-    @contextlib.contextmanager
     def offset_view(shape, dt):
-        """ones in a view 8 bytes off the 16-byte alignment of the packed kernels, as tests/test_gpu_math_ops.py::_Offset"""
-        x = np.ones(shape, dtype=dt)
-        raw = B.dsc_device_alloc(_get_ctx(), x.nbytes + 256)
-        view = dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), raw + 8, x.nbytes, x.ndim, (ctypes.c_int * x.ndim)(*shape), NP_TO_DTYPE[x.dtype].value))
-        B.dsc_copy_from_host(_get_ctx(), view._c_ptr, x.ctypes.data, x.nbytes)
-        try:
-            yield view
-        finally:
-            del view
-            dsc.synchronize()
-            B.dsc_device_free(_get_ctx(), raw)
+        return offset_ones(dsc, np, shape, dt)
 
     def unary_and_cast(x, dt, what):
         for name in UNARY:
