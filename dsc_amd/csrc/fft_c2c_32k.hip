@@ -1,8 +1,8 @@
 // fft_c2c_32k.hip — 32768-point complex transform of c32 rows (dsc_fft / dsc_ifft, dsc_fft.h:156-176): the three passes of
-// fft_r2c_64k.hip without a real pass, in its own translation unit (adding a kernel to that file perturbed the register
-// allocation of the 65536-point kernels, which sit exactly at 128 VGPRs).
-#define DSC_R2C64K_HELPERS_ONLY 1
-#include "fft_r2c_64k.hip"
+// fft_r2c_64k.hip (fft_64k_common.h) without a real pass, in its own translation unit (adding a kernel to that file perturbed
+// the register allocation of the 65536-point kernels, which sit exactly at 128 VGPRs), and with the decimation-in-frequency
+// butterflies: the Linzer-Feig form measured slower here (0.835 against 0.824 ms).
+#include "fft_64k_common.h"
 
 namespace {
 
@@ -42,7 +42,7 @@ __global__ __launch_bounds__(1024) void c2c32k_kernel(const f2 *__restrict__ z, 
         const __amdgpu_buffer_rsrc_t rnext = __builtin_amdgcn_make_buffer_rsrc(
             (void *) ((const char *) z + (size_t) next_row * in_pitch * EB), 0, next_row < batch ? in_len * EB : 0, 0x00020000);
         const __amdgpu_buffer_rsrc_t rout = __builtin_amdgcn_make_buffer_rsrc((void *) (Z + (size_t) row * kM), 0, kM * 8, 0x00020000);
-        three_passes<INV>(v, plane, T, aux, wave_sgpr, wave_sgpr, false, false);      // v[p] = Z[t + 1024 br5(p)], t = reader_column
+        three_passes<INV, kDif>(v, plane, T, aux, wave_sgpr, wave_sgpr, false, false);      // v[p] = Z[t + 1024 br5(p)], t = reader_column
         if (INV) {
 #pragma unroll
             for (int p = 0; p < 32; ++p) v[p] = cf{v[p].x * kScale, v[p].y * kScale};
@@ -66,10 +66,8 @@ __global__ __launch_bounds__(1024) void c2c32k_kernel(const f2 *__restrict__ z, 
 // z: [batch][in_pitch] c32 (cast: f32) of which in_len <= 32768 samples are transformed; Z: [batch][32768] c32
 void dsc_launch_fft32k_c32(const void *z, void *Z, int batch, int in_pitch, int in_len, bool inverse, bool cast, const void *aux, int n_cu,
                            hipStream_t stream) {
-    if (batch <= 0) return;
-    const int grid = batch < n_cu ? batch : n_cu;
     with_bool(inverse, [&](auto inv) { with_bool(cast, [&](auto c) {
-        dsc_launch_dyn_lds<c2c32k_kernel<decltype(inv)::value, decltype(c)::value>>(grid, 1024, kLdsBytes, stream, (const f2 *) z, (f2 *) Z, batch,
-                                                                                    (const f2 *) aux, in_pitch, in_len);
+        launch_rows<c2c32k_kernel<decltype(inv)::value, decltype(c)::value>>(batch, n_cu, stream, (const f2 *) z, (f2 *) Z, batch, (const f2 *) aux,
+                                                                             in_pitch, in_len);
     }); });
 }

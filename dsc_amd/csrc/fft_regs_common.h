@@ -1,7 +1,8 @@
-// fft_regs_common.h — device building blocks of the register-resident FFT kernels (fft_regs_mid.hip,
-// fft_r2c_2pass.hip): complex arithmetic, in-register radix-2 DIF DFTs of 2..32 points with
-// compile-time twiddles (results in bit-reversed register order), the LDS-only barrier and buffer
-// load / store wrappers.  Header-only, everything in an anonymous namespace.
+// fft_regs_common.h — device building blocks of the register-resident FFT kernels (fft_regs_mid.hip, fft_regs_cols.hip,
+// fft_r2c_2pass.hip, fft_xcd_fused.hip, fft_tiny.hip, fft_2d.hip and, through fft_64k_common.h, fft_r2c_64k.hip and
+// fft_c2c_32k.hip): complex arithmetic, in-register radix-2 DFTs of 2..32 points with compile-time twiddles (natural order in,
+// results in bit-reversed register order) in two forms, decimation in time (the default) and in frequency, chosen by a template
+// argument of dft_n, the LDS-only barrier and buffer load / store wrappers.  Header-only, everything in an anonymous namespace.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -60,7 +61,7 @@ __device__ __forceinline__ cpx<R> mul_root(cpx<R> d) {
     }
 }
 
-#ifdef DSC_DFT_DIF
+// The decimation-in-frequency butterflies: subtract, then multiply by W_M^K.  Group G of a stage covers v[BASE + G M .. + M).
 template<typename R, bool INV, int M, int G, int... K>
 __device__ __forceinline__ void dif_group(cpx<R> (&v)[32], std::integer_sequence<int, K...>) {
     (([&] {
@@ -75,22 +76,14 @@ template<typename R, bool INV, int M, int BASE, int... G>
 __device__ __forceinline__ void dif_stage(cpx<R> (&v)[32], std::integer_sequence<int, G...>) {
     (dif_group<R, INV, M, BASE + G * M>(v, std::make_integer_sequence<int, M / 2>{}), ...);
 }
-// N-point DFT (N = 2 .. 32) of v[BASE .. BASE+N), natural order in; v[BASE + p] returns bin brev(p, log2 N)
-template<typename R, bool INV, int N, int BASE = 0>
-__device__ __forceinline__ void dft_n(cpx<R> (&v)[32]) {
-    if constexpr (N >= 32) dif_stage<R, INV, 32, BASE>(v, std::make_integer_sequence<int, N / 32>{});
-    if constexpr (N >= 16) dif_stage<R, INV, 16, BASE>(v, std::make_integer_sequence<int, N / 16>{});
-    if constexpr (N >= 8)  dif_stage<R, INV, 8, BASE>(v, std::make_integer_sequence<int, N / 8>{});
-    if constexpr (N >= 4)  dif_stage<R, INV, 4, BASE>(v, std::make_integer_sequence<int, N / 4>{});
-    dif_stage<R, INV, 2, BASE>(v, std::make_integer_sequence<int, N / 2>{});
-}
-#else
+
 // The decimation-in-time graph with natural-order input and bit-reversed output (same contract as the DIF form above): stage s
 // (half distance H = N >> s) has 2^(s-1) groups, group g multiplies the LOWER input of its butterflies by ONE constant
 // e^{-i pi theta_g}, theta_g = brev(g, s-1) / 2^(s-1) — a DFT with frequency offset theta splits into two of offsets theta / 2
 // and (1 + theta) / 2 — then adds and subtracts.  A constant twiddle in FRONT of the add / sub costs 6 fused multiply-adds
 // instead of the 8 operations of "subtract, then multiply" (Linzer & Feig): w = c (1 + i t), p = b.x - t b.y, q = b.y + t b.x,
-// out = a +- c (p, q); the larger of |cos|, |sin| is factored out so that |t| <= 1.
+// out = a +- c (p, q); the larger of |cos|, |sin| is factored out so that |t| <= 1.  34 of the 80 butterflies of a 32-point
+// transform carry such a twiddle: 388 VALU instructions instead of 456.
 __device__ __forceinline__ float fma_r(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_r(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
@@ -137,22 +130,31 @@ template<typename R, bool INV, int N, int S, int BASE, int... G>
 __device__ __forceinline__ void dit_stage(cpx<R> (&v)[32], std::integer_sequence<int, G...>) {
     (dit_group<R, INV, N, S, BASE, G>(v, std::make_integer_sequence<int, (N >> S)>{}), ...);
 }
-// N-point DFT (N = 2 .. 32) of v[BASE .. BASE+N), natural order in; v[BASE + p] returns bin brev(p, log2 N)
-template<typename R, bool INV, int N, int BASE = 0>
-__device__ __forceinline__ void dft_n(cpx<R> (&v)[32]) {
-    dit_stage<R, INV, N, 1, BASE>(v, std::make_integer_sequence<int, 1>{});
-    if constexpr (N >= 4)  dit_stage<R, INV, N, 2, BASE>(v, std::make_integer_sequence<int, 2>{});
-    if constexpr (N >= 8)  dit_stage<R, INV, N, 3, BASE>(v, std::make_integer_sequence<int, 4>{});
-    if constexpr (N >= 16) dit_stage<R, INV, N, 4, BASE>(v, std::make_integer_sequence<int, 8>{});
-    if constexpr (N >= 32) dit_stage<R, INV, N, 5, BASE>(v, std::make_integer_sequence<int, 16>{});
+// Stage S of the N-point transform at v[BASE ..), groups G... of its 2^(S-1) only, in either form: both number their groups alike,
+// group G covers the N >> (S-1) registers from BASE + G (N >> (S-1)).  Which form a kernel uses is decided where it calls.
+constexpr bool kDit = false, kDif = true;
+template<typename R, bool INV, int N, int S, int BASE, bool DIF, int... G>
+__device__ __forceinline__ void dft_stage(cpx<R> (&v)[32], std::integer_sequence<int, G...> groups) {
+    if constexpr (DIF) dif_stage<R, INV, (N >> (S - 1)), BASE>(v, groups);
+    else dit_stage<R, INV, N, S, BASE>(v, groups);
 }
-#endif
+// N-point DFT (N = 2 .. 32) of v[BASE .. BASE+N), natural order in; v[BASE + p] returns bin brev(p, log2 N)
+template<typename R, bool INV, int N, int BASE = 0, bool DIF = kDit>
+__device__ __forceinline__ void dft_n(cpx<R> (&v)[32]) {
+    dft_stage<R, INV, N, 1, BASE, DIF>(v, std::make_integer_sequence<int, 1>{});
+    if constexpr (N >= 4)  dft_stage<R, INV, N, 2, BASE, DIF>(v, std::make_integer_sequence<int, 2>{});
+    if constexpr (N >= 8)  dft_stage<R, INV, N, 3, BASE, DIF>(v, std::make_integer_sequence<int, 4>{});
+    if constexpr (N >= 16) dft_stage<R, INV, N, 4, BASE, DIF>(v, std::make_integer_sequence<int, 8>{});
+    if constexpr (N >= 32) dft_stage<R, INV, N, 5, BASE, DIF>(v, std::make_integer_sequence<int, 16>{});
+}
 template<typename R, bool INV, int N, int... I>
 __device__ __forceinline__ void dft_columns(cpx<R> (&v)[32], std::integer_sequence<int, I...>) {
     (dft_n<R, INV, N, I * N>(v), ...);
 }
 
-// LDS-only barrier: does not wait for outstanding global loads / stores
+// LDS-only barrier: does not wait for outstanding global loads / stores.  __syncthreads() also drains vmcnt, i.e. every wave
+// would wait at each barrier (about 12 per row in the 65536-point kernels) for its outstanding global stores and prefetched
+// loads; nothing in these kernels communicates through global memory.
 __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     __builtin_amdgcn_s_barrier();

@@ -4,7 +4,8 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=fast -fno-slp-vectorize -Iinclude -Idsc_amd/csrc tools/probe64k.hip -o tools/bin/probe64k
 //   tools/bin/probe64k [batch]
 #define DSC_R2C64K_PROBE 1
-#include "../dsc_amd/csrc/fft_r2c_64k.hip"
+#include "../dsc_amd/csrc/fft_64k_common.h"      // the building blocks
+#include "../dsc_amd/csrc/fft_r2c_64k.hip"       // the kernels, with their io_on argument
 
 #include <algorithm>
 #include <cstdio>

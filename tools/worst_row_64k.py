@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 # usage: [DSC_MI355X_LIB=<build>.so] tools/worst_row_64k.py [--save DIR]
 # The worst row (rel-L2 against float64 numpy) of the five operators that share
-# three_passes() of fft_r2c_64k.hip, on 300 seeded rows; DSC_MI355X_LIB selects the build.  --save writes the raw outputs to
+# three_passes() of fft_64k_common.h, on 300 seeded rows; DSC_MI355X_LIB selects the build.  --save writes the raw outputs to
 # DIR/<op>.npy (to compare two builds bit by bit).
 import os
 import sys
