@@ -7,11 +7,14 @@ import subprocess
 import sys
 
 import numpy as np
+import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 GOLDEN = os.path.join(HERE, 'golden')
 NP = {'f32': np.float32, 'f64': np.float64, 'c32': np.complex64, 'c64': np.complex128}
+F32, F64, C64, C128 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.complex64), np.dtype(np.complex128)
+CPX = {F32: C64, F64: C128}
 
 # Tolerances of BASELINE.json's north_star ("within 1e-5 rel of CPU reference"; 1e-12 for
 # the f64 config) — relative L2 error against the reference/oracle output.
@@ -64,27 +67,95 @@ def assert_close(actual, expected, tol=None, what=''):
     assert e2 <= tol and em <= tol * 4, f'{what}: rel_l2={e2:.3e} max_rel={em:.3e} tol={tol:g}'
 
 
-def device_view(dsc, big, shape, dt):
-    """A Tensor of `shape` / numpy dtype `dt` over the start of the device buffer of `big` (not owned): the out= target of the GPU
-    route tests, which fill `big` with a sentinel and check that nothing past the view changes."""
+# ---------------------------------------------------------------------------------------------------- the GPU tests' scaffold
+
+@pytest.fixture(scope='module')
+def dsc():
+    """The one context of a pytest process, 14 GiB main + 5 GiB scratch whichever module asks first (init refuses a second call, so
+    differing sizes per module would let the collection order choose).  GPU test modules import it by name; each leaves the device idle."""
+    import dsc_amd
+    try:
+        dsc_amd.init(14 << 30, 5 << 30)
+    except RuntimeWarning:
+        pass
+    yield dsc_amd
+    dsc_amd.synchronize()
+
+
+def sync_fixture(*switches):
+    """The autouse fixture of a GPU test module (`_sync = sync_fixture('DSC_SCAN_ROUTE')`): every test starts and ends with the
+    named environment switches unset and ends with the device idle."""
+    def clear():
+        for name in switches:
+            os.environ.pop(name, None)
+
+    @pytest.fixture(autouse=True)
+    def _sync(dsc):
+        clear()
+        yield
+        dsc.synchronize()
+        clear()
+    return _sync
+
+
+def device_view(dsc, big, shape, dt, byte_offset=0):
+    """A Tensor of `shape` / numpy dtype `dt` over the device buffer of `big` from `byte_offset` on (not owned): the out= target of the
+    GPU route tests, which fill `big` with a sentinel and check that nothing outside the view changes."""
     from dsc_amd import _bindings as B
     from dsc_amd.context import _get_ctx
     from dsc_amd.dtype import NP_TO_DTYPE
     dt = np.dtype(dt)
     c_shape = (ctypes.c_int * len(shape))(*shape)
     nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
+    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data + byte_offset, nbytes, len(shape), c_shape,
+                                                   NP_TO_DTYPE[dt].value))
+
+
+def assert_out_call(dsc, call, shape, dt, first, what=''):
+    """call(out) into the start of a sentinel-filled buffer with 4099 spare elements: the bits of `first` (the result of the same call
+    without out=), the tail untouched"""
+    dt = np.dtype(dt)
+    size = int(np.prod(shape))
+    sentinel = np.asarray(-7.25 + 3.5j if dt.kind == 'c' else -7.25, dtype=dt)
+    big = dsc.from_numpy(np.full(size + 4099, sentinel, dtype=dt))
+    out = device_view(dsc, big, list(shape), dt)
+    call(out)
+    whole = big.numpy()
+    what = what and what + ': '
+    assert whole[:size].tobytes() == first.tobytes(), f'{what}two identical calls differ (or out= was not written)'
+    assert np.all(whole[size:] == sentinel), f'{what}bytes past the output changed'
+
+
+def run_child(code, env=None, without=(), timeout=300, check=False, args=()):
+    """`python -c code *args` from the repository root, the variables `without` taken out of its environment and `env` added: the
+    CompletedProcess.  With check, exit status 0 is asserted and the ends of its output shown."""
+    e = {k: v for k, v in os.environ.items() if k not in without}
+    e.update(env or {})
+    r = subprocess.run([sys.executable, '-c', code, *args], cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=e)
+    if check:
+        assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-2000:])
+    return r
 
 
 def assert_ends_the_process(stmt, message, without_env=None):
     """`stmt` after dsc.init(1 << 28, 1 << 24) in a child process, the variable `without_env` taken out of its environment: a message
     on stderr and exit status 1; nothing runs on the GPU after it."""
     code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
-    env = {k: v for k, v in os.environ.items() if k != without_env}
-    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300, env=env)
+    r = run_child(code, without=(without_env,))
     assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
     assert message in r.stderr, r.stderr[-400:]
     assert 'HIP error' not in r.stderr and 'illegal memory' not in r.stderr
+
+
+def build_cpp_smoke(tmp_path, name):
+    """tests/<name>.cpp compiled with the host compiler against the C++ API header and linked to the library: the executable's path"""
+    exe = str(tmp_path / name)
+    cmd = ['g++', '-std=c++17', '-Wall', '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'dsc_amd', 'api'),
+           os.path.join(ROOT, 'tests', name + '.cpp'), '-L' + os.path.join(ROOT, 'dsc_amd'), '-ldsc_mi355x',
+           '-Wl,-rpath,' + os.path.join(ROOT, 'dsc_amd'), '-Wl,-rpath-link,/opt/rocm/lib', '-o', exe]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return exe
 
 
 class Golden:

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import build_cpp_smoke
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 HEADER = os.path.join(ROOT, 'include', 'dsc_mi355x.h')
 LIB = os.path.join(ROOT, 'dsc_amd', 'libdsc_mi355x.so')
@@ -148,16 +150,6 @@ def test_block_plan_sample_by_sample():
 
 
 def test_cpp_conv_smoke_compiles_and_links(tmp_path):
-    exe = build_cpp_conv_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_conv_smoke')
     r = subprocess.run([exe, '0'], capture_output=True, text=True)
     assert r.returncode == 0 and 'linked' in r.stdout
-
-
-def build_cpp_conv_smoke(tmp_path):
-    exe = str(tmp_path / 'cpp_conv_smoke')
-    cmd = ['g++', '-std=c++17', '-Wall', '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'dsc_amd', 'api'),
-           os.path.join(ROOT, 'tests', 'cpp_conv_smoke.cpp'), '-L' + os.path.join(ROOT, 'dsc_amd'), '-ldsc_mi355x',
-           '-Wl,-rpath,' + os.path.join(ROOT, 'dsc_amd'), '-Wl,-rpath-link,/opt/rocm/lib', '-o', exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe

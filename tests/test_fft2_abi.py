@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import build_cpp_smoke
 from tests.test_fft_ref import pow2, real_of, ref_fft
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
@@ -189,17 +190,7 @@ def test_expect_path_windows():
 
 # ---------------------------------------------------------------------------------------------------- C++
 
-def build_cpp_fft2_smoke(tmp_path):
-    exe = str(tmp_path / 'cpp_fft2_smoke')
-    cmd = ['g++', '-std=c++17', '-Wall', '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'dsc_amd', 'api'),
-           os.path.join(ROOT, 'tests', 'cpp_fft2_smoke.cpp'), '-L' + os.path.join(ROOT, 'dsc_amd'), '-ldsc_mi355x',
-           '-Wl,-rpath,' + os.path.join(ROOT, 'dsc_amd'), '-Wl,-rpath-link,/opt/rocm/lib', '-o', exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
 def test_cpp_fft2_smoke_compiles_and_links(tmp_path):
-    exe = build_cpp_fft2_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_fft2_smoke')
     r = subprocess.run([exe, '0'], capture_output=True, text=True)
     assert r.returncode == 0 and 'linked' in r.stdout

@@ -8,22 +8,11 @@ or a wrong row of it shows up in the bins of a few columns only, which a norm ov
 import numpy as np
 import pytest
 
-from tests.helpers import assert_close, rel_l2
+from tests.helpers import assert_close, dsc, rel_l2  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 N = 65536
 M = N // 2
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(14 << 30, 5 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-    dsc_amd.synchronize()
 
 
 def rows_close(got, want, what):

@@ -17,7 +17,7 @@ max-rel <= 4e-5 per row): an impulse response is a product of at most four float
 import numpy as np
 import pytest
 
-from tests.helpers import TOL, assert_close
+from tests.helpers import TOL, assert_close, dsc  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 N = 65536
@@ -26,17 +26,6 @@ ROWS = 600
 POSITIONS = (0, 1, 1023, 1024, 32767, 65535)
 OPS = ('rfft', 'irfft', 'filter_fft', 'fft', 'ifft')
 PATHS = {'rfft': 'r2c_64k_regs', 'irfft': 'c2r_64k_regs', 'filter_fft': 'filter_64k_regs', 'fft': 'c2c_32k_regs', 'ifft': 'c2c_32k_regs'}
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(14 << 30, 5 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-    dsc_amd.synchronize()
 
 
 @pytest.fixture(scope='module')

@@ -2,39 +2,22 @@
 f32 and f64, filter lengths 1 .. 16383 (conv_regs) and 40000 (conv_composed), rows shorter than one block, odd, 2^k + 1 and ~300 000
 samples long, [T] / [B, T] / [2, 3, T] inputs; impulses at the block edges for every store alignment; the DSC_NO_CONV_FUSED switch, a
 tightly sized context, no writes past the output or into the next row, determinism, argument errors, one full-size [64, 2^20] case and the C++ API."""
-import ctypes
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.test_conv_abi import build_cpp_conv_smoke, conv_plan, conv_span, np_convolve_fft
+from tests.helpers import build_cpp_smoke, device_view, dsc, run_child, sync_fixture  # noqa: F401
+from tests.test_conv_abi import conv_plan, conv_span, np_convolve_fft
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 TOL = {np.float32: 1e-5, np.float64: 1e-12}
 MS = (1, 2, 3, 16, 63, 255, 256, 1000, 4097, 16383)
 TS = (300, 1001, 4097, 300007)          # below one block, odd, 2^k + 1, ~300 000
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 def row_rel(got, want):
@@ -119,14 +102,6 @@ def test_long_filter_takes_composed(dsc, fn, dtype):
         assert row_rel(got, np_convolve_fft(x, h, mode, correlate=fn == 'correlate')) <= TOL[dtype]
 
 
-def _child(code, env=None, timeout=600):
-    e = dict(os.environ)
-    e.update(env or {})
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=e)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout
-
-
 SWITCH = '''
 import json, sys, numpy as np, dsc_amd as dsc
 dsc.init(4 << 30, 2 << 30)
@@ -145,8 +120,9 @@ print(json.dumps(res))
 def test_switch_selects_composed_and_agrees_with_fused(tmp_path):
     (tmp_path / 'f').mkdir()
     (tmp_path / 'c').mkdir()
-    fused = json.loads(_child(SWITCH.replace('sys.argv[1]', repr(str(tmp_path / 'f')))).strip().splitlines()[-1])
-    composed = json.loads(_child(SWITCH.replace('sys.argv[1]', repr(str(tmp_path / 'c'))), {'DSC_NO_CONV_FUSED': '1'}).strip().splitlines()[-1])
+    fused = run_child(SWITCH, timeout=600, check=True, args=(str(tmp_path / 'f'),))
+    composed = run_child(SWITCH, {'DSC_NO_CONV_FUSED': '1'}, timeout=600, check=True, args=(str(tmp_path / 'c'),))
+    fused, composed = (json.loads(r.stdout.strip().splitlines()[-1]) for r in (fused, composed))
     assert set(fused.values()) == {'conv_regs'} and set(composed.values()) == {'conv_composed'}
     for i in fused:
         a, b = np.load(tmp_path / 'f' / f'{i}.npy'), np.load(tmp_path / 'c' / f'{i}.npy')
@@ -171,24 +147,18 @@ print('TIGHT OK', e)
 
 
 def test_tight_context_chunks():
-    assert 'TIGHT OK' in _child(TIGHT)
+    assert 'TIGHT OK' in run_child(TIGHT, timeout=600, check=True).stdout
 
 
 @pytest.mark.parametrize('dtype,T,M,mode', [(np.float32, 10001, 255, 'full'), (np.float64, 4097, 16383, 'same'),
                                              (np.float32, 30001, 40000, 'full'), (np.float64, 777, 3, 'valid')])
 def test_no_stray_writes(dsc, dtype, T, M, mode):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
     rows = 3
     n0, T_out = conv_span(T, M, mode)
     extra = 70000
     sentinel = np.full(rows * T_out + extra, -7.25, dtype=dtype)
     big = dsc.from_numpy(sentinel)
-    shape = (ctypes.c_int * 2)(rows, T_out)
-    es = np.dtype(dtype).itemsize
-    out = dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, rows * T_out * es, 2, shape,
-                                                  NP_TO_DTYPE[np.dtype(dtype)].value))
+    out = device_view(dsc, big, (rows, T_out), dtype)
     rng = np.random.default_rng(T)
     x, h = rng.standard_normal((rows, T)).astype(dtype), rng.standard_normal(M).astype(dtype)
     _run(dsc, 'convolve', x, h, mode, out=out)
@@ -278,6 +248,6 @@ def test_full_size_against_oracle(dsc):
 
 
 def test_cpp_conv_templates_on_gpu(tmp_path):
-    exe = build_cpp_conv_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_conv_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'conv templates ok' in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])

@@ -17,41 +17,21 @@ Every route, old and new, is below 0.5, so TAU stays as it is.
 Every case asserts dsc.last_fft_path() (expect_path restates the routing), checks that the input is left bit for bit unchanged, and
 repeats the call with out= the head of a larger sentinel-filled buffer: the result must be bit-identical and nothing past it may
 change.  Steps that end a process (argument errors) or need their own context (the tight arena) run in child processes."""
-import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.test_fft2_abi import (FUSED_DIMS, FUSED_REAL_COLS, build_cpp_fft2_smoke, expect_path, fused_group, out_shape2, ref_fft2)
+from tests.helpers import (C128, CPX, F32, F64, assert_ends_the_process, assert_out_call, build_cpp_smoke, dsc,  # noqa: F401
+                           run_child, sync_fixture)
+from tests.test_fft2_abi import FUSED_DIMS, FUSED_REAL_COLS, expect_path, fused_group, out_shape2, ref_fft2
 from tests.test_fft_ref import TAU, fft_err, real_of
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-F32, F64, C64, C128 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.complex64), np.dtype(np.complex128)
-CPX = {F32: C64, F64: C128}
 KINDS2 = ('fft2', 'ifft2', 'rfft2', 'irfft2')
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    os.environ.pop('DSC_NO_FFT2_FUSED', None)
-    yield
-    os.environ.pop('DSC_NO_FFT2_FUSED', None)
-    dsc.synchronize()
+_sync = sync_fixture('DSC_NO_FFT2_FUSED')
 
 
 # ---------------------------------------------------------------------------------------------------- inputs and checks
@@ -87,15 +67,6 @@ def transform_sizes(kind, shape, s):
     return o[-2], (2 * (o[-1] - 1) if kind == 'rfft2' else o[-1])
 
 
-def _view(dsc, big, shape, dt):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
-    c_shape = (ctypes.c_int * len(shape))(*shape)
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
-
-
 def err_ratio(yh, x, s, kind, images=None):
     """largest err / bound over the images (all, or the listed ones), each flattened to one line"""
     oshape = yh.shape
@@ -125,17 +96,10 @@ def run_case(dsc, record_property, kind, x, s, images=None, fused_off=False):
     assert X.numpy().tobytes() == x.tobytes(), 'the input changed'
     del y
 
-    extra = 4099
-    size = int(np.prod(oshape))
-    sentinel = np.asarray(-7.25 + 3.5j if odt.kind == 'c' else -7.25, dtype=odt)
-    big = dsc.from_numpy(np.full(size + extra, sentinel, dtype=odt))
-    out = _view(dsc, big, oshape, odt)
-    fn(X, out=out, s=s)
-    assert dsc.last_fft_path() == want_path
-    whole = big.numpy()
-    assert whole[:size].tobytes() == yh.tobytes(), 'two identical calls differ (or out= was not written)'
-    assert np.all(whole[size:] == sentinel), 'bytes past the output changed'
-    del out, big
+    def again(out):
+        fn(X, out=out, s=s)
+        assert dsc.last_fft_path() == want_path
+    assert_out_call(dsc, again, oshape, odt, yh)
 
     r = err_ratio(yh, x, s, kind, images)
     record_property(f'{want_path}:{kind}:{x.dtype}', r)
@@ -329,13 +293,6 @@ def test_round_trips(dsc, rdt, N0, N1):
 
 # ---------------------------------------------------------------------------------------------------- child processes
 
-def _child(code, timeout=300, env=None):
-    e = dict(os.environ)
-    e.pop('DSC_NO_FFT2_FUSED', None)
-    e.update(env or {})
-    return subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=e)
-
-
 TIGHT = r'''
 import sys
 import numpy as np
@@ -366,7 +323,7 @@ print('tight ok')
 def test_fused_route_needs_no_intermediate(kind, dt, N0, N1):
     """a context with room for x and out and 1 MiB: the fused route runs; the composed one would need an intermediate of out's size"""
     B = (32 << 20) // (N0 * N1 * np.dtype(dt).itemsize)
-    r = subprocess.run([sys.executable, '-c', TIGHT, kind, dt, str(N0), str(N1), str(B)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_child(TIGHT, args=(kind, dt, str(N0), str(N1), str(B)))
     assert r.returncode == 0 and 'tight ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])
     assert ('path rfft2_regs' if kind == 'rfft2' else 'path fft2_regs') in r.stdout
 
@@ -385,15 +342,11 @@ ERRORS = {
 @pytest.mark.parametrize('name', sorted(ERRORS))
 def test_argument_errors_end_the_process(name):
     """like every operator: a message on stderr and a non-zero exit; nothing runs on the GPU after it"""
-    stmt, message = ERRORS[name]
-    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
-    r = _child(code)
-    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
-    assert message in r.stderr, r.stderr[-400:]
+    assert_ends_the_process(*ERRORS[name], without_env='DSC_NO_FFT2_FUSED')
 
 
 def test_cpp_fft2_smoke_on_the_gpu(tmp_path):
-    exe = build_cpp_fft2_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_fft2_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'fft2 templates ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])
 

@@ -9,38 +9,16 @@ ragged for every column tile width (8 .. 256); odd inner extents on the real fou
 dimensions; zero padded and cropped lines (irfft: fewer and more bins than order + 1, imaginary parts in bins 0 and order); plain
 noise plus lines with a large DC offset or one strong tone.  Routes behind an environment switch run in a child process, as do the
 tight-context fallbacks of the axis four-step routes."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from tests.helpers import device_view as _view
+from tests.helpers import C64, C128, CPX, F32, F64, assert_out_call, dsc, run_child, sync_fixture  # noqa: F401
 from tests.test_fft_ref import TAU, fft_err, out_len, pow2, real_of, ref_fft
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-F32, F64, C64, C128 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.complex64), np.dtype(np.complex128)
-CPX = {F32: C64, F64: C128}
 LDS_MAX = {True: 8192, False: 4096}                     # dsc_fft_lds_max_len
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 # ------------------------------------------------------------------------------------- the routes table of fft_driver.cpp, restated
@@ -187,17 +165,10 @@ def run_case(dsc, record_property, kind, x, n, axis):
     assert X.numpy().tobytes() == x.tobytes(), 'the input changed'
     del y
 
-    extra = 4099
-    size = int(np.prod(oshape))
-    sentinel = np.asarray(-7.25 + 3.5j if odt.kind == 'c' else -7.25, dtype=odt)
-    big = dsc.from_numpy(np.full(size + extra, sentinel, dtype=odt))
-    out = _view(dsc, big, oshape, odt)
-    fn(X, out=out, n=n, axis=axis)
-    assert dsc.last_fft_path() == want_path
-    whole = big.numpy()
-    assert whole[:size].tobytes() == yh.tobytes(), 'two identical calls differ (or out= was not written)'
-    assert np.all(whole[size:] == sentinel), 'bytes past the output changed'
-    del out, big
+    def again(out):
+        fn(X, out=out, n=n, axis=axis)
+        assert dsc.last_fft_path() == want_path
+    assert_out_call(dsc, again, oshape, odt, yh)
 
     # cols_4step_real: two neighbouring real columns go through one complex column, each carries rounding of the pair's size
     r = fft_err(yh, ref_fft(x, n, axis, kind), axis, TAU[real_of(x.dtype)], paired=want_path == 'cols_4step_real')
@@ -404,9 +375,7 @@ SWITCH_CASES = {
 def test_switched_off_routes(record_property, tmp_path, switches):
     cases = SWITCH_CASES[switches]
     code = 'CASES = %r\nOUT = %r\n' % ([c[:5] for c in cases], str(tmp_path)) + SWITCHED
-    env = dict(os.environ, **{k: '1' for k in switches.split()})
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    r = run_child(code, env={k: '1' for k in switches.split()}, timeout=600, check=True)
     paths = [ln.split()[2] for ln in r.stdout.splitlines() if ln.startswith('PATH')]
     assert paths == [c[5] for c in cases], paths
     for i, (kind, dt, shape, n, axis, path) in enumerate(cases):
@@ -444,7 +413,7 @@ print('OK', path, r, flush=True)
 def _tight(kind, rows, cols, dt, need, spare, roomy):
     code = TIGHT.replace('KIND', repr(kind)).replace('ROWS', str(rows)).replace('COLS', str(cols)).replace('DT', repr(dt)) \
         .replace('NEED', str(need)).replace('SPARE', str(spare)).replace('ROOMY', str(roomy))
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = run_child(code, timeout=600)
     assert r.returncode == 0 and 'OK' in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-1500:])
     return r.stdout.split('OK')[-1].split()
 

@@ -9,37 +9,20 @@ Routes (dsc.last_fft_path()):
 Row counts that leave a ragged last workgroup for every lines-per-group count, odd / padded / cropped row lengths, [ls], [rows, ls] and
 [2, 3, ls] inputs, filters with a single nonzero bin at each edge of the spectrum (bins 0 and n/2 with an imaginary part that must be
 ignored), known answers (identity, circular shifts, impulses), out= views with a sentinel tail, and determinism."""
-import ctypes
-
 import numpy as np
 import pytest
 
+from tests.helpers import CPX, F32, F64, device_view, dsc, sync_fixture  # noqa: F401
 from tests.test_filter_ref import TAU, filter_err, ref_filter, used
 
 pytestmark = pytest.mark.gpu
 
-F32, F64, C32, C64 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.complex64), np.dtype(np.complex128)
-CPX = {F32: C32, F64: C64}
+C32, C64 = CPX[F32], CPX[F64]
 MID_N = (512, 1024, 2048, 4096, 8192, 16384, 32768)
 FUSED = [(n, dt) for dt in (F32, F64) for n in MID_N] + [(65536, F32)]
 COMPOSED_N = (4, 64, 256)
 FUSED_IDS = [f'{n}-{dt}' for n, dt in FUSED]
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 def route(n, sdt, hdt, ls):
@@ -225,15 +208,10 @@ def test_impulses(dsc, record_property, n, dt):
     ids=lambda v: str(v))
 def test_out_and_no_stray_writes(dsc, record_property, n, sdt, hdt, rows, ls):
     """out= a view of the start of a larger sentinel-filled device buffer: the result lands in it, and nothing past rows * n changes."""
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
     odt = sdt if CPX[sdt] == hdt else F64
     extra = 70000
     big = dsc.from_numpy(np.full(rows * n + extra, -7.25, dtype=odt))
-    shape = (ctypes.c_int * 2)(rows, n)
-    out = dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, rows * n * odt.itemsize, 2, shape,
-                                                  NP_TO_DTYPE[odt].value))
+    out = device_view(dsc, big, (rows, n), odt)
     rng = np.random.default_rng([n, rows, ls])
     s = rng.standard_normal((rows, ls)).astype(sdt)
     H = rand_H(rng, n, hdt)

@@ -4,28 +4,14 @@ Every case prints enough to be replayed (`seed`, `case index`).  Tolerances as t
 import numpy as np
 import pytest
 
-from tests.helpers import assert_close
+from tests.helpers import assert_close, dsc, sync_fixture  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 REAL = (np.float32, np.float64)
 CPLX = (np.complex64, np.complex128)
 
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 def _rand(rng, shape, dt):

@@ -6,21 +6,10 @@ C ABI.  Tolerance: rel-L2 <= 1e-5 (north_star)."""
 import numpy as np
 import pytest
 
-from tests.helpers import assert_close, rel_l2
+from tests.helpers import assert_close, dsc, rel_l2  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 N = 65536
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(14 << 30, 5 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-    dsc_amd.synchronize()
 
 
 def test_paths_are_the_hand_written_kernels(dsc):

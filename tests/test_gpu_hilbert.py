@@ -19,54 +19,25 @@ Every case asserts dsc.last_fft_path() (expect_path restates the routing), check
 the real part of hilbert is bit for bit the row as the transform read it, and repeats the call with out= the head of a larger
 sentinel-filled buffer: the result must be bit-identical and nothing past it may change.  Steps that end a process (argument errors)
 or need their own context (the tight arena) run in child processes."""
-import ctypes
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
+from tests.helpers import (CPX, F32, F64, assert_ends_the_process, assert_out_call, build_cpp_smoke, dsc, run_child,  # noqa: F401
+                           sync_fixture)
 from tests.test_filter_ref import TAU, used
-from tests.test_hilbert_abi import (FUSED_GROUP, KINDS, build_cpp_hilbert_smoke, expect_path, hilbert_err, length_of, ref_envelope, ref_hilbert,
-                                    spiced_rows)
+from tests.test_hilbert_abi import FUSED_GROUP, KINDS, expect_path, hilbert_err, length_of, ref_envelope, ref_hilbert, spiced_rows
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-F32, F64, C64, C128 = np.dtype(np.float32), np.dtype(np.float64), np.dtype(np.complex64), np.dtype(np.complex128)
-CPX = {F32: C64, F64: C128}
 FUSED_LENGTHS = sorted(FUSED_GROUP[F32])
 SWITCH = 'DSC_NO_HILBERT_FUSED'
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    os.environ.pop(SWITCH, None)
-    yield
-    os.environ.pop(SWITCH, None)
-    dsc.synchronize()
+_sync = sync_fixture(SWITCH)
 
 
 # ---------------------------------------------------------------------------------------------------- checks
-
-def _view(dsc, big, shape, dt):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
-    c_shape = (ctypes.c_int * len(shape))(*shape)
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
-
 
 def err_ratio(kind, yh, x, n, rows=None):
     """largest err / bound over the rows (all, or the listed ones)"""
@@ -102,17 +73,10 @@ def run_case(dsc, record_property, kind, x, n=None, rows=None, fused_off=False):
         assert np.ascontiguousarray(yh.real).tobytes() == used(x, N).tobytes(), 'the real part is not the row'
     del y
 
-    extra = 4099
-    size = int(np.prod(oshape))
-    sentinel = np.asarray(-7.25 + 3.5j if odt.kind == 'c' else -7.25, dtype=odt)
-    big = dsc.from_numpy(np.full(size + extra, sentinel, dtype=odt))
-    out = _view(dsc, big, oshape, odt)
-    fn(X, n=n, out=out)
-    assert dsc.last_fft_path() == want_path
-    whole = big.numpy()
-    assert whole[:size].tobytes() == yh.tobytes(), 'two identical calls differ (or out= was not written)'
-    assert np.all(whole[size:] == sentinel), 'bytes past the output changed'
-    del out, big
+    def again(out):
+        fn(X, n=n, out=out)
+        assert dsc.last_fft_path() == want_path
+    assert_out_call(dsc, again, oshape, odt, yh)
 
     r = err_ratio(kind, yh, x, n, rows)
     record_property(f'{want_path}:{x.dtype}', r)
@@ -272,13 +236,6 @@ def test_envelope_against_absolute_of_hilbert(dsc, dt, N, fused_off):
 
 # ---------------------------------------------------------------------------------------------------- child processes
 
-def _child(code, timeout=300, env=None):
-    e = dict(os.environ)
-    e.pop(SWITCH, None)
-    e.update(env or {})
-    return subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=timeout, env=e)
-
-
 TIGHT = r'''
 import sys
 import numpy as np
@@ -307,7 +264,7 @@ print('tight ok')
 def test_fused_route_needs_no_scratch(kind, dt, N):
     """a context with room for x, out and 1 MiB, and 1 MiB of scratch: the fused route runs; the composed one needs a chunk"""
     B = (32 << 20) // (N * np.dtype(dt).itemsize)
-    r = subprocess.run([sys.executable, '-c', TIGHT, kind, dt, str(N), str(B)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    r = run_child(TIGHT, args=(kind, dt, str(N), str(B)))
     assert r.returncode == 0 and 'tight ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])
     assert f'path {kind}_regs' in r.stdout
 
@@ -359,8 +316,7 @@ def test_composed_route_in_several_chunks(tmp_path, record_property, kind, dt, N
     x = spiced_rows(np.random.default_rng([N, dt.itemsize, 11]), rows, N, dt)
     src, dst = str(tmp_path / 'x.npy'), str(tmp_path / 'y.npy')
     np.save(src, x)
-    r = subprocess.run([sys.executable, '-c', CHUNKS, kind, str(scratch), src, dst], cwd=ROOT, capture_output=True, text=True, timeout=300,
-                       env=dict(os.environ, **{SWITCH: '1'}))
+    r = run_child(CHUNKS, env={SWITCH: '1'}, args=(kind, str(scratch), src, dst))
     assert r.returncode == 0 and 'chunks ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])
     assert f'path {kind}_composed' in r.stdout
     yh = np.load(dst)
@@ -387,15 +343,11 @@ ERRORS = {
 @pytest.mark.parametrize('name', sorted(ERRORS))
 def test_argument_errors_end_the_process(name):
     """like every operator: a message on stderr and exit status 1; nothing runs on the GPU after it"""
-    stmt, message = ERRORS[name]
-    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
-    r = _child(code)
-    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
-    assert message in r.stderr, r.stderr[-400:]
+    assert_ends_the_process(*ERRORS[name], without_env=SWITCH)
 
 
 def test_cpp_hilbert_smoke_on_the_gpu(tmp_path):
-    exe = build_cpp_hilbert_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_hilbert_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'hilbert templates ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])
 

@@ -3,28 +3,14 @@ handle lifetime (double frees, handles that outlive dsc.clear(): dsc/src/dsc.cpp
 (dsc_ops.h:318-339), the tall-skinny reduction and an axis-0 transform in an arena with no room for the transpose route."""
 import ctypes
 import gc
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.helpers import assert_close, rel_l2
+from tests.helpers import ROOT, dsc, rel_l2, run_child  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 REAL, COMPLEX = 0, 1
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
 
 
 def test_plan_fft_hit_eviction_and_clear(dsc):
@@ -179,7 +165,7 @@ assert err <= 1e-5, err
 # with room, the same call takes the transpose route: same answer
 print('OK', path, err)
 ''' % ROOT
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=600)
+    r = run_child(code, timeout=600)
     assert r.returncode == 0 and 'OK' in r.stdout, (r.stdout[-500:], r.stderr[-1500:])
     assert 'generic' in r.stdout, r.stdout             # no room for the transposes: the strided LDS kernel took it
 
@@ -206,5 +192,5 @@ print('OK', path, dsc.last_fft_path())
 ''' % ROOT
     for scratch_mb, env, want in ((256, {}, 'r2c_fused_l2 c2r_fused_l2'), (12, {}, 'r2c_2pass_regs c2r_2pass_regs'),
                                   (256, {'DSC_NO_FUSED_L2': '1'}, 'r2c_2pass_regs c2r_2pass_regs')):
-        r = subprocess.run([sys.executable, '-c', code, str(scratch_mb)], capture_output=True, text=True, timeout=600, env={**os.environ, **env})
+        r = run_child(code, env, timeout=600, args=(str(scratch_mb),))
         assert r.returncode == 0 and ('OK ' + want) in r.stdout, (scratch_mb, env, r.stdout[-300:], r.stderr[-800:])

@@ -9,28 +9,13 @@ import os
 import numpy as np
 import pytest
 
-from tests.helpers import GOLDEN, assert_ends_the_process, rel_l2
+from tests.helpers import GOLDEN, assert_ends_the_process, build_cpp_smoke, dsc, rel_l2, sync_fixture  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 UNARY = ('cos', 'sin', 'sinc', 'logn', 'log2', 'log10', 'exp', 'sqrt')
 NP_UNARY = {'cos': np.cos, 'sin': np.sin, 'sinc': np.sinc, 'logn': np.log, 'log2': np.log2, 'log10': np.log10, 'exp': np.exp, 'sqrt': np.sqrt}
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 def assert_matches(got, want, rel, floor, what=''):
@@ -467,7 +452,6 @@ def test_kaiser_fir_designed_and_applied_on_device(dsc):
 
 def test_cpp_math_templates_on_gpu(tmp_path):
     import subprocess
-    from tests.test_math_ops_abi import build_cpp_math_smoke
-    exe = build_cpp_math_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_math_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'math templates ok' in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])

@@ -30,9 +30,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests.helpers import TOL, assert_ends_the_process, device_view
-from tests.test_moments_abi import (C32, C64, F32, F64, LD, REAL_OF, Moments, build_cpp_moments_smoke, gamma, lay, moment_rows,
-                                    reduced_shape)
+from tests.helpers import TOL, assert_ends_the_process, build_cpp_smoke, device_view, dsc, sync_fixture  # noqa: F401
+from tests.test_moments_abi import C32, C64, F32, F64, LD, REAL_OF, Moments, gamma, lay, moment_rows, reduced_shape
 
 pytestmark = pytest.mark.gpu
 
@@ -47,29 +46,18 @@ SWEEP = (('sumsq', 0, True), ('rms', 0, False), ('var', 0, True), ('var', 1, Fal
 WORST = {}
 
 
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(2 << 30, 1 << 28)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-    os.environ.pop('DSC_MOMENT_ROUTE', None)
+_sync = sync_fixture('DSC_MOMENT_ROUTE')
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _report(dsc):
+    yield
     report = os.environ.get('DSC_MOMENTS_REPORT')                   # tools and job scripts: the table of profiles/moments_err.md
     if report:
         with open(report, 'w') as fh:
             fh.write('| operator | dtype | route | worst err / bound |\n|---|---|---|---|\n')
             for (op, dt, route), r in sorted(WORST.items()):
                 fh.write(f'| {op} | {dt} | {route} | {r:.4g} |\n')
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    os.environ.pop('DSC_MOMENT_ROUTE', None)
-    yield
-    dsc.synchronize()
-    os.environ.pop('DSC_MOMENT_ROUTE', None)
 
 
 def force(route):
@@ -316,6 +304,6 @@ def test_detrend_type_names(dsc):
 
 
 def test_cpp_moments_smoke_on_the_gpu(tmp_path):
-    exe = build_cpp_moments_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_moments_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'moment templates ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])

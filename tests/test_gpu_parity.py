@@ -2,31 +2,13 @@
 (1) the committed golden fixtures = outputs of the reference itself, and (2) the CPU oracle on
 seeded inputs.  Tolerance is BASELINE.json's: relative L2 <= 1e-5 for f32, 1e-12 for f64
 (tests/helpers.py:TOL), max/min exact."""
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from tests.helpers import assert_close, rel_l2
+from tests.helpers import assert_close, dsc, rel_l2, run_child, sync_fixture  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 OPS = ('fft', 'ifft', 'rfft', 'irfft')
@@ -317,7 +299,7 @@ def test_errors_abort_like_the_reference():
     }
     for name, stmt in cases.items():
         code = f'import numpy as np, dsc_amd as dsc\ndsc.init(1 << 26, 1 << 26)\n{stmt}\ndsc.synchronize()\nprint("SURVIVED")'
-        r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True)
+        r = run_child(code, timeout=None)
         assert r.returncode != 0 and 'SURVIVED' not in r.stdout, (name, r.stdout, r.stderr)
         assert 'RFFT input must be real' in r.stderr or 'IRFFT input must be complex' in r.stderr or 'DSC_ASSERT' in r.stderr, name
 
@@ -438,7 +420,7 @@ def test_indexing_errors_abort_like_the_reference():
     for name, stmt in cases.items():
         code = ('import numpy as np, dsc_amd as dsc\ndsc.init(1 << 26, 1 << 26)\n'
                 f't = dsc.from_numpy(np.zeros((3, 4), np.float32))\n{stmt}\ndsc.synchronize()\nprint("SURVIVED")')
-        r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True)
+        r = run_child(code, timeout=None)
         assert r.returncode != 0 and 'SURVIVED' not in r.stdout, (name, r.stdout, r.stderr)
         assert 'dsc_tensor_' in r.stderr or 'DSC_ASSERT' in r.stderr, (name, r.stderr)      # "<entry point>: <the rule that failed>"
 

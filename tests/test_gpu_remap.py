@@ -6,16 +6,15 @@ Every case asserts dsc.last_fft_path() against the route the plan's statement ex
 unchanged, repeats the call with out= the head of a larger sentinel-filled buffer (bit-identical, nothing past it touched) and, on
 the pack routes, repeats it under DSC_REMAP_ROUTE=elems and compares bit for bit.  Argument errors end the process and run in child
 processes."""
-import ctypes
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests.helpers import assert_ends_the_process
-from tests.test_remap_abi import (C32, C64, ELEMS, F32, F64, PACKS, PAD_MODES, ROWS, bits, build_cpp_remap_smoke, map_flip, map_identity, map_roll,
-                                  pad_maps, random_bits, ref_fftshift, ref_flip, ref_ifftshift, ref_pad, ref_roll, route)
+from tests.helpers import assert_ends_the_process, build_cpp_smoke, device_view, dsc, sync_fixture  # noqa: F401
+from tests.test_remap_abi import (C32, C64, ELEMS, F32, F64, PACKS, PAD_MODES, ROWS, bits, map_flip, map_identity, map_roll, pad_maps,
+                                  random_bits, ref_fftshift, ref_flip, ref_ifftshift, ref_pad, ref_roll, route)
 
 pytestmark = pytest.mark.gpu
 
@@ -23,34 +22,7 @@ DTYPES = [F32, F64, C32, C64]
 LENGTHS = (1, 2, 3, 4, 5, 7, 8, 9, 15, 16, 17, 255, 256, 257, 1023, 1024, 1025, 4097)
 SENTINEL = -7.25
 EXTRA = 1031
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(2 << 30, 1 << 28)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-    os.environ.pop('DSC_REMAP_ROUTE', None)
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    os.environ.pop('DSC_REMAP_ROUTE', None)
-    yield
-    dsc.synchronize()
-    os.environ.pop('DSC_REMAP_ROUTE', None)
-
-
-def _view(dsc, big, shape, dt, byte_offset=0):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
-    c_shape = (ctypes.c_int * len(shape))(*shape)
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data + byte_offset, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
+_sync = sync_fixture('DSC_REMAP_ROUTE')
 
 
 def same(a, b):
@@ -66,7 +38,7 @@ def check(dsc, call, X, x, want, path):
     assert same(yh, want), (path, x.shape, x.dtype)
     del y
     big = dsc.from_numpy(np.full(want.size + EXTRA, SENTINEL, dtype=x.dtype))
-    out = _view(dsc, big, want.shape, x.dtype)
+    out = device_view(dsc,big, want.shape, x.dtype)
     call(out)
     assert dsc.last_fft_path() == path
     whole = big.numpy()
@@ -239,7 +211,7 @@ def test_a_base_off_the_pack_boundary_leaves_the_pack_routes(dsc):
     flat = np.concatenate([np.zeros(2, F32), x.reshape(-1), np.zeros(2, F32)])
     big = dsc.from_numpy(flat)
     assert big._c_ptr.contents.data % 16 == 0
-    Xo = _view(dsc, big, x.shape, F32, byte_offset=8)
+    Xo = device_view(dsc,big, x.shape, F32, byte_offset=8)
     assert same(Xo.numpy(), x)
     for f, want in ((lambda out: dsc.roll(Xo, 1, axis=-1, out=out), ref_roll(x, 1, -1)), (lambda out: dsc.roll(Xo, 1, axis=0, out=out), ref_roll(x, 1, 0)),
                     (lambda out: dsc.pad(Xo, ((0, 0), (4, 4)), mode='reflect', out=out), ref_pad(x, ((0, 0), (4, 4)), 'reflect'))):
@@ -247,7 +219,7 @@ def test_a_base_off_the_pack_boundary_leaves_the_pack_routes(dsc):
         assert dsc.last_fft_path() == ELEMS
     X = dsc.from_numpy(x)
     dest = dsc.from_numpy(np.full(x.size + 8, SENTINEL, F32))
-    out = _view(dsc, dest, x.shape, F32, byte_offset=8)
+    out = device_view(dsc,dest, x.shape, F32, byte_offset=8)
     for f, want in ((lambda: dsc.roll(X, 1, axis=-1, out=out), ref_roll(x, 1, -1)), (lambda: dsc.roll(X, 1, axis=0, out=out), ref_roll(x, 1, 0))):
         f()
         assert dsc.last_fft_path() == ELEMS
@@ -298,6 +270,6 @@ def test_an_unknown_mode_name_is_a_python_error(dsc):
 
 
 def test_cpp_remap_smoke_on_the_gpu(tmp_path):
-    exe = build_cpp_remap_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_remap_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'remap templates ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])

@@ -13,51 +13,22 @@ The largest guaranteed shapes: (160, 1) 0.30 / 0.26, (1, 160) 0.0004 / 0.0008, 4
 Every case asserts dsc.last_fft_path(), checks that the input is left bit for bit unchanged, and repeats the call with out= the head of
 a larger sentinel-filled buffer: the result must be bit-identical and nothing past it may change.  Argument errors end the process and
 run in child processes."""
-import ctypes
-import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.test_resample_abi import (build_cpp_resample_smoke, polyphase_err, ref_magnitude, ref_polyphase, resample_plan, spiced_rows,
-                                     upfirdn_plan)
+from tests.helpers import F32, F64, assert_ends_the_process, assert_out_call, build_cpp_smoke, dsc, sync_fixture  # noqa: F401
+from tests.test_resample_abi import polyphase_err, ref_magnitude, ref_polyphase, resample_plan, spiced_rows, upfirdn_plan
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-F32, F64 = np.dtype(np.float32), np.dtype(np.float64)
 DIRECT, COPY = 'polyphase_direct', 'polyphase_copy'
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(2 << 30, 1 << 28)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 def _dtype(dsc, dt):
     return dsc.Dtype.F32 if dt == F32 else dsc.Dtype.F64
-
-
-def _view(dsc, big, shape, dt):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
-    c_shape = (ctypes.c_int * len(shape))(*shape)
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
 
 
 def run_case(dsc, record_property, op, call, x, h, plan):
@@ -75,16 +46,10 @@ def run_case(dsc, record_property, op, call, x, h, plan):
     assert X.numpy().tobytes() == x.tobytes(), 'the input changed'
     del y
 
-    extra = 4099
-    size = int(np.prod(oshape))
-    big = dsc.from_numpy(np.full(size + extra, -7.25, dtype=dt))
-    out = _view(dsc, big, oshape, dt)
-    call(X, out)
-    assert dsc.last_fft_path() == DIRECT
-    whole = big.numpy()
-    assert whole[:size].tobytes() == yh.tobytes(), 'two identical calls differ (or out= was not written)'
-    assert np.all(whole[size:] == -7.25), 'bytes past the output changed'
-    del out, big
+    def again(out):
+        call(X, out)
+        assert dsc.last_fft_path() == DIRECT
+    assert_out_call(dsc, again, oshape, dt, yh)
 
     by_phase = x.shape[-1] * up * len(h) > 4_000_000
     K = -(-len(h) // up)
@@ -258,15 +223,10 @@ ERRORS = {
 @pytest.mark.parametrize('name', sorted(ERRORS))
 def test_argument_errors_end_the_process(name):
     """like every operator: a message on stderr and exit status 1; nothing runs on the GPU after it"""
-    stmt, message = ERRORS[name]
-    code = f"import numpy as np\nimport dsc_amd as dsc\ndsc.init(1 << 28, 1 << 24)\n{stmt}\nprint('survived')\n"
-    r = subprocess.run([sys.executable, '-c', code], cwd=ROOT, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 1 and 'survived' not in r.stdout, (r.returncode, r.stdout[-300:], r.stderr[-300:])
-    assert message in r.stderr, r.stderr[-400:]
-    assert 'HIP error' not in r.stderr and 'illegal memory' not in r.stderr
+    assert_ends_the_process(*ERRORS[name])
 
 
 def test_cpp_resample_smoke_on_the_gpu(tmp_path):
-    exe = build_cpp_resample_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_resample_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'resample templates ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])

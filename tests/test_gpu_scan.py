@@ -20,16 +20,15 @@ to f32, the bound's first term; in f64 the one rounding of the FMA uses a fifth 
 Every case asserts dsc.last_fft_path(), checks that the input is left bit for bit unchanged, and repeats the call with out= the head of
 a larger sentinel-filled buffer: the result must be bit-identical and nothing past it may change.  DSC_SCAN_ROUTE forces scan_rows or
 scan_tiles on the inner == 1 shapes.  Argument errors end the process and run in child processes."""
-import ctypes
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests.helpers import assert_ends_the_process
-from tests.test_scan_abi import (C32, C64, F32, F64, UNIT, assert_away_from_ties, build_cpp_scan_smoke, cumsum_err, cumsum_rows,
-                                 multi_wrap_rows, ref_unwrap, smooth_rows, unwrap_err, wrapped_chirps)
+from tests.helpers import assert_ends_the_process, build_cpp_smoke, device_view, dsc, sync_fixture  # noqa: F401
+from tests.test_scan_abi import (C32, C64, F32, F64, UNIT, assert_away_from_ties, cumsum_err, cumsum_rows, multi_wrap_rows, ref_unwrap,
+                                 smooth_rows, unwrap_err, wrapped_chirps)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,34 +36,7 @@ ROWS, TILES, COLS, DIFF = 'scan_rows', 'scan_tiles', 'scan_cols', 'scan_diff'
 # every length around a power of two up to 2^16, and 70001: the pack, wave, chunk and tile boundaries of every dtype lie among them
 T_LAST = sorted({t for k in range(17) for t in (2 ** k - 1, 2 ** k, 2 ** k + 1) if t >= 1} | {70001})
 REAL_OF = {C32: F32, C64: F64}
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(2 << 30, 1 << 28)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-    os.environ.pop('DSC_SCAN_ROUTE', None)
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    os.environ.pop('DSC_SCAN_ROUTE', None)
-    yield
-    dsc.synchronize()
-    os.environ.pop('DSC_SCAN_ROUTE', None)
-
-
-def _view(dsc, big, shape, dt):
-    from dsc_amd import _bindings as B
-    from dsc_amd.context import _get_ctx
-    from dsc_amd.dtype import NP_TO_DTYPE
-    c_shape = (ctypes.c_int * len(shape))(*shape)
-    nbytes = int(np.prod(shape)) * dt.itemsize
-    return dsc.Tensor(B.dsc_tensor_from_device_ptr(_get_ctx(), big._c_ptr.contents.data, nbytes, len(shape), c_shape, NP_TO_DTYPE[dt].value))
+_sync = sync_fixture('DSC_SCAN_ROUTE')
 
 
 def force(route):
@@ -95,7 +67,7 @@ def run(dsc, op, x, axis, path, forced=True):
     extra = 1031
     size = int(np.prod(oshape))
     big = dsc.from_numpy(np.full(size + extra, -7.25, dtype=odt))
-    out = _view(dsc, big, oshape, odt)
+    out = device_view(dsc, big, oshape, odt)
     f(X, axis=axis, out=out)
     assert dsc.last_fft_path() == path
     whole = big.numpy()
@@ -353,6 +325,6 @@ def test_argument_errors_end_the_process(name):
 
 
 def test_cpp_scan_smoke_on_the_gpu(tmp_path):
-    exe = build_cpp_scan_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_scan_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'scan templates ok' in r.stdout, (r.returncode, r.stdout[-400:], r.stderr[-400:])

@@ -9,35 +9,19 @@ import itertools
 import json
 import os
 import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from tests.test_stft_abi import build_cpp_stft_smoke, np_istft, np_stft
+from tests.helpers import build_cpp_smoke, dsc, run_child, sync_fixture  # noqa: F401
+from tests.test_stft_abi import np_istft, np_stft
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 FUSED = (64, 256, 1024, 4096, 32768)
 COMPOSED = (4, 32, 65536, 262144)
 TOL = {np.float32: 1e-5, np.float64: 1e-12}
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 def rel(a, b):
@@ -114,14 +98,6 @@ def test_stft_matches_numpy(dsc, n_fft, hop, dtype, center, pad_mode, shape, win
     assert rel(got, want) <= TOL[dtype], (path, rel(got, want))
 
 
-def _child(code, env=None, timeout=600):
-    e = dict(os.environ)
-    e.update(env or {})
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=e)
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
-    return r.stdout
-
-
 SWITCH = '''
 import json, sys, numpy as np, dsc_amd as dsc
 dsc.init(4 << 30, 2 << 30)
@@ -139,10 +115,9 @@ print(json.dumps(res))
 def test_switch_selects_composed_and_agrees_with_fused(tmp_path):
     (tmp_path / 'f').mkdir()
     (tmp_path / 'c').mkdir()
-    code = SWITCH.replace('sys.argv[1]', repr(str(tmp_path / 'f')))
-    fused = json.loads(_child(code).strip().splitlines()[-1])
-    code = SWITCH.replace('sys.argv[1]', repr(str(tmp_path / 'c')))
-    composed = json.loads(_child(code, {'DSC_NO_STFT_FUSED': '1'}).strip().splitlines()[-1])
+    fused = run_child(SWITCH, timeout=600, check=True, args=(str(tmp_path / 'f'),))
+    composed = run_child(SWITCH, {'DSC_NO_STFT_FUSED': '1'}, timeout=600, check=True, args=(str(tmp_path / 'c'),))
+    fused, composed = (json.loads(r.stdout.strip().splitlines()[-1]) for r in (fused, composed))
     assert set(fused.values()) == {'stft_regs'} and set(composed.values()) == {'stft_composed'}
     for n in fused:
         a, b = np.load(tmp_path / 'f' / f'{n}.npy'), np.load(tmp_path / 'c' / f'{n}.npy')
@@ -172,7 +147,7 @@ print('TIGHT OK', e1, e2)
 
 
 def test_tight_context_chunks():
-    assert 'TIGHT OK' in _child(TIGHT)
+    assert 'TIGHT OK' in run_child(TIGHT, timeout=600, check=True).stdout
 
 
 @pytest.mark.parametrize('n_fft,hop,center,win,length', [
@@ -267,6 +242,6 @@ def test_full_size_against_numpy_and_composed(dsc):
 
 
 def test_cpp_stft_templates_on_gpu(tmp_path):
-    exe = build_cpp_stft_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_stft_smoke')
     r = subprocess.run([exe, '1'], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and 'stft templates ok' in r.stdout, (r.stdout[-1500:], r.stderr[-1500:])

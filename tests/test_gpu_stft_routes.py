@@ -14,22 +14,15 @@ with nonzero imaginary parts in bins 0 and n_fft / 2, not the stft of a signal.
 Sizes kept down for the host reference, whose long-double transforms are the cost of a case: above n_fft 4096 the odd hop is
 n / 8 + 1 (at most about 30 frames per row); at 262144 (forward) and from 131072 (inverse) signals are n_fft + n_fft / 2 + 7 long /
 spectra have 5 frames instead of 9, and the batch shapes are [.], [2, .] and [1, 2, .]."""
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
-from tests.helpers import device_view
+from tests.helpers import CPX, F32, F64, assert_out_call, dsc, run_child, sync_fixture  # noqa: F401
 from tests.test_fft_ref import TAU, real_of
 from tests.test_stft_ref import hann, istft_err, odd_hop, rand_spectrum, rand_window, ref_istft, ref_stft, stft_err
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-F32, F64 = np.dtype(np.float32), np.dtype(np.float64)
-CPX = {F32: np.dtype(np.complex64), F64: np.dtype(np.complex128)}
 FUSED = tuple(1 << k for k in range(6, 16))                                                 # 64 .. 32768: dsc_stft_regs_supports
 COMPOSED = (4, 8, 16, 32, 65536, 262144)
 INVERSE = tuple(1 << k for k in range(2, 19))                                               # 4 .. 262144
@@ -39,22 +32,7 @@ INVERSE = tuple(1 << k for k in range(2, 19))                                   
 # 32768 run fft_mid_kernel with G = mid_cfg<R, B, TWO>::G = NT / T (frames never take the persistent one-line form).
 GROUP = {64: (128, 128), 128: (64, 64), 256: (32, 32), 512: (16, 16), 1024: (8, 16), 2048: (4, 4), 4096: (4, 2), 8192: (2, 1),
          16384: (2, 1), 32768: (1, 1)}                                                       # n_fft: (f32, f64)
-
-
-@pytest.fixture(scope='module')
-def dsc():
-    import dsc_amd
-    try:
-        dsc_amd.init(12 << 30, 4 << 30)
-    except RuntimeWarning:
-        pass
-    yield dsc_amd
-
-
-@pytest.fixture(autouse=True)
-def _sync(dsc):
-    yield
-    dsc.synchronize()
+_sync = sync_fixture()
 
 
 # ---------------------------------------------------------------------------------------------------- inputs and checks
@@ -77,18 +55,6 @@ def stft_route(n_fft):
     return 'stft_regs' if 64 <= n_fft <= 32768 else 'stft_composed'
 
 
-def _sentinel_call(dsc, call, shape, odt, yh, what):
-    """call(out) into the start of a sentinel-filled buffer with 4099 spare elements: the same bits, the tail untouched"""
-    size = int(np.prod(shape))
-    sentinel = np.asarray(-7.25 + 3.5j if odt.kind == 'c' else -7.25, dtype=odt)
-    big = dsc.from_numpy(np.full(size + 4099, sentinel, dtype=odt))
-    out = device_view(dsc, big, list(shape), odt)
-    call(out)
-    whole = big.numpy()
-    assert whole[:size].tobytes() == yh.tobytes(), f'{what}: two identical calls differ (or out= was not written)'
-    assert np.all(whole[size:] == sentinel), f'{what}: bytes past the output changed'
-
-
 def run_stft(dsc, record_property, x, n_fft, hop, w, center, pad_mode, want_path=None, label=''):
     """dsc.stft on the GPU: the route, the input and the window left alone, every frame within the bound, and a second call into a
     sentinel-filled buffer.  Returns err / bound."""
@@ -109,7 +75,7 @@ def run_stft(dsc, record_property, x, n_fft, hop, w, center, pad_mode, want_path
     def again(out):
         dsc.stft(X, n_fft, hop, W, center, pad_mode, out=out)
         assert dsc.last_fft_path() == want_path
-    _sentinel_call(dsc, again, yh.shape, yh.dtype, yh, what)
+    assert_out_call(dsc, again, yh.shape, yh.dtype, yh, what)
     r = stft_err(yh, want, TAU[x.dtype])
     record_property(f'{want_path}:stft:{n_fft}:{x.dtype}', r)
     print(f'{what}: err / bound = {r:.3g}')
@@ -135,7 +101,7 @@ def run_istft(dsc, record_property, X, n_fft, hop, w, center, length, label=''):
     def again(out):
         dsc.istft(Xt, n_fft, hop, W, center, length, out=out)
         assert dsc.last_fft_path() == 'istft_ola'
-    _sentinel_call(dsc, again, yh.shape, yh.dtype, yh, what)
+    assert_out_call(dsc, again, yh.shape, yh.dtype, yh, what)
     r = istft_err(yh, want, bound, TAU[rdt])
     record_property(f'istft_ola:istft:{n_fft}:{rdt}', r)
     print(f'{what}: err / bound = {r:.3g}')
@@ -281,9 +247,7 @@ def test_switch_takes_the_composed_route_at_every_fused_length(record_property, 
     per-frame bound."""
     cases = [(n, odd_hop(n), dt.name) for n in FUSED for dt in (F32, F64)]
     code = 'CASES = %r\nOUT = %r\n' % (cases, str(tmp_path)) + SWITCHED
-    r = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=300, cwd=ROOT,
-                       env=dict(os.environ, DSC_NO_STFT_FUSED='1'))
-    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-2000:])
+    r = run_child(code, env={'DSC_NO_STFT_FUSED': '1'}, check=True)
     paths = [ln.split()[3] for ln in r.stdout.splitlines() if ln.startswith('PATH')]
     assert paths == ['stft_composed'] * len(cases), paths
     for n, hop, dt in cases:
@@ -367,7 +331,7 @@ print('CHUNKED OK', flush=True)
 
 def _chunked(cases, chunk, timeout=300):
     code = 'CASES = %r\n' % (cases,) + CHUNKED.replace('N_CHUNK', str(chunk))
-    return subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, timeout=timeout, cwd=ROOT)
+    return run_child(code, timeout=timeout)
 
 
 def _record_chunked(record_property, r):

@@ -19,6 +19,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import build_cpp_smoke
 from tests.test_fft_ref import pow2
 from tests.test_filter_ref import TAU, ref_filter, used
 
@@ -135,19 +136,9 @@ def test_cpp_wrappers_and_documents():
 
 
 def test_cpp_hilbert_smoke_compiles_and_links(tmp_path):
-    exe = build_cpp_hilbert_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_hilbert_smoke')
     r = subprocess.run([exe, '0'], capture_output=True, text=True)
     assert r.returncode == 0 and 'linked' in r.stdout
-
-
-def build_cpp_hilbert_smoke(tmp_path):
-    exe = str(tmp_path / 'cpp_hilbert_smoke')
-    cmd = ['g++', '-std=c++17', '-Wall', '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'dsc_amd', 'api'),
-           os.path.join(ROOT, 'tests', 'cpp_hilbert_smoke.cpp'), '-L' + os.path.join(ROOT, 'dsc_amd'), '-ldsc_mi355x',
-           '-Wl,-rpath,' + os.path.join(ROOT, 'dsc_amd'), '-Wl,-rpath-link,/opt/rocm/lib', '-o', exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
 
 
 # ---- the reference is the textbook and scipy's ---------------------------------------------------------------------------------

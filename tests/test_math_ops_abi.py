@@ -10,6 +10,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import build_cpp_smoke
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
 LIB = os.path.join(ROOT, 'dsc_amd', 'libdsc_mi355x.so')
@@ -111,16 +113,6 @@ def test_regenerated_cases_reproduce_the_fixtures():
 
 def test_cpp_math_templates_compile_and_link(lib, tmp_path):
     """dsc::cos .. sqrt, pow, i0, clip, arange, randn, reshape, concat of dsc_amd/api/dsc_api.h with a host compiler."""
-    exe = build_cpp_math_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_math_smoke')
     r = subprocess.run([exe, '0'], capture_output=True, text=True)
     assert r.returncode == 0 and 'linked' in r.stdout
-
-
-def build_cpp_math_smoke(tmp_path):
-    exe = str(tmp_path / 'cpp_math_smoke')
-    cmd = ['g++', '-std=c++17', '-Wall', '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'dsc_amd', 'api'),
-           os.path.join(ROOT, 'tests', 'cpp_math_smoke.cpp'), '-L' + os.path.join(ROOT, 'dsc_amd'), '-ldsc_mi355x',
-           '-Wl,-rpath,' + os.path.join(ROOT, 'dsc_amd'), '-Wl,-rpath-link,/opt/rocm/lib', '-o', exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe

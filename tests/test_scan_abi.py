@@ -23,6 +23,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests.helpers import build_cpp_smoke
+
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
 HEADER = os.path.join(ROOT, 'include', 'dsc_mi355x.h')
 LIB = os.path.join(ROOT, 'dsc_amd', 'libdsc_mi355x.so')
@@ -189,18 +191,8 @@ def test_cpp_wrappers_and_documents():
             assert name in text, (doc, name)
 
 
-def build_cpp_scan_smoke(tmp_path):
-    exe = str(tmp_path / 'cpp_scan_smoke')
-    cmd = ['g++', '-std=c++17', '-Wall', '-I' + os.path.join(ROOT, 'include'), '-I' + os.path.join(ROOT, 'dsc_amd', 'api'),
-           os.path.join(ROOT, 'tests', 'cpp_scan_smoke.cpp'), '-L' + os.path.join(ROOT, 'dsc_amd'), '-ldsc_mi355x',
-           '-Wl,-rpath,' + os.path.join(ROOT, 'dsc_amd'), '-Wl,-rpath-link,/opt/rocm/lib', '-o', exe]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    return exe
-
-
 def test_cpp_scan_smoke_compiles_and_links(tmp_path):
-    exe = build_cpp_scan_smoke(tmp_path)
+    exe = build_cpp_smoke(tmp_path, 'cpp_scan_smoke')
     r = subprocess.run([exe, '0'], capture_output=True, text=True)
     assert r.returncode == 0 and 'linked' in r.stdout
 
